@@ -24,8 +24,6 @@ import time
 
 import numpy as np
 
-# one HIP hardware queue per step in flight (the runtime's default of 4 would make streams share queues)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 os.environ.setdefault("OCTA_STRICT", "1")      # a measured pass that leaves the hand-written kernels for the vendor libraries is an error (models/networks.py)
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -451,6 +449,45 @@ def train_cli_leg(n_graphs=128, epochs=4, extra_args=()):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_SAMPLES = 4           # samples of the last step written in full: 4 x (two 1216^2 labels + one 304^2 image) in float32 = 49 MB
+DUMP_LIMIT = 64_000_000    # bytes, all files together
+
+
+def dump_outputs(d, out, batch, seeds):
+    """--dump-outputs: what the timed path returned for its LAST step (the last `batch` samples of the last launch), written as
+    d/<name>.npy in float64 / float32 so that two builds can be compared output for output. For every sample of the step: its
+    seed, edge count and arterial edge count; for a fixed seeded choice of DUMP_SAMPLES of them (samples.npy, indices into the
+    step): the edge list in the reference's CSV row order (edges.npy, rows edge_off[j]:edge_off[j + 1] for the j-th chosen
+    sample), the 304 x 304 image, the grey 1216 x 1216 label raster and the binarised label."""
+    import torch
+    r = out["result"]
+    first = len(r) - batch
+    off = np.asarray(r.edge_off, np.int64)[first:]
+    pick = np.sort(np.random.default_rng(0).choice(batch, size=min(DUMP_SAMPLES, batch), replace=False))
+
+    def rows(j):
+        a, b = int(off[j]), int(off[j + 1])
+        return r.d_edges[a:b].cpu().numpy() if r.d_edges is not None else r.edges[a:b]
+
+    edges = [rows(j) for j in pick]
+    arrays = {"seeds": np.asarray(seeds, np.float64),
+              "n_edges": np.diff(off).astype(np.float64),
+              "n_art": np.asarray(r.n_art, np.float64)[first:],
+              "samples": pick.astype(np.float64),
+              "edges": np.concatenate(edges).astype(np.float64),
+              "edge_off": np.concatenate([[0], np.cumsum([len(e) for e in edges])]).astype(np.float64)}
+    idx = torch.as_tensor(first + pick, device=out["image"].device)
+    for k in ("image", "label_grey", "label"):
+        arrays[k] = out[k].index_select(0, idx).cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than the {DUMP_LIMIT} allowed")
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    print(f"[bench] outputs of the last timed step written to {d} ({total / 1e6:.1f} MB)", file=sys.stderr)
+
+
 def launcher_selftest(args):
     """The N-rank skeleton of main() with a stub body, on gloo (no GPU): process group from the launcher's environment, the rank count by
     all-reduce, a barrier-bracketed timed region, MAX of the wall time over ranks, per-rank values by all-gather, ONE JSON line from rank 0."""
@@ -513,8 +550,12 @@ def main():
                     "steps of 4 over all ranks; about a minute on one MI355X). Round 5: part of the DEFAULT run, so that the driver's line carries end_to_end_10k_epoch")
     ap.add_argument("--long", dest="long", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)      # tests/test_bench_launcher.py: the launcher + one-line contract on gloo ranks, no GPU
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (rank 0) as "
+                    "DIR/<name>.npy, float32 / float64, at most 64 MB: see dump_outputs()")
     ap.set_defaults(long=True)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.pmc_child:
         pmc_child(args.batch)
         return
@@ -610,7 +651,7 @@ def main():
             if outs and not same_gen:
                 finish(slot, outs[-1])
             o = launch(slot, f0, n, wait=False)
-            o["steps"] = n
+            o["first_step"], o["steps"] = f0, n
             if outs and same_gen:
                 finish(slot, outs[-1])
             outs.append(o)
@@ -658,6 +699,9 @@ def main():
         dt = time.time() - t0
     finally:
         gc.enable()
+    if args.dump_outputs and rank == 0:
+        last = args.warmup + args.steps - 1
+        dump_outputs(args.dump_outputs, next(o for o in outs if o["first_step"] + o["steps"] == last + 1), B, sharding.rank_seeds(rank, last, B))
     # where a slot's time goes (host clock, mean over the timed launches): simulator call (host init + kernel + download + BFS export),
     # render enqueue, wait for the render kernels; `kernel` is the device time of the persistent kernel inside the simulator call
     slot_cycle = None

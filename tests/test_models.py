@@ -45,10 +45,13 @@ def test_dice_bce_formula():
 
 
 def _worker(rank, world, port, out):
+    # a CPU rank: torch's Python-level device queries (torch.cuda.is_available(), its optimisers' too) see no GPU here, as on a CPU box
+    os.environ.update(HIP_VISIBLE_DEVICES="", PYTORCH_NVML_BASED_CUDA_CHECK="1")
     import torch.distributed as dist
     from octa_autosegmentation_amd.models.segmentation_trainer import SegmentationTrainer
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.set_num_threads(1)                           # the same reduction order as the reference step of the test
     torch.manual_seed(100 + rank)                      # different init per rank: must be overwritten by rank 0's
     tr = SegmentationTrainer(CFG, "cpu", channels_last=False)
     g = torch.Generator().manual_seed(7)
@@ -70,10 +73,16 @@ def test_two_rank_data_parallel_step_equals_single_process_batch(tmp_path):
     ref = SegmentationTrainer(CFG, "cpu", channels_last=False)
     g = torch.Generator().manual_seed(7)
     x = torch.rand(2, 1, 32, 32, generator=g); y = (torch.rand(2, 1, 32, 32, generator=g) > 0.6).float()
-    # mean over ranks of per-rank (batch 1) gradients == gradient of the mean of the two per-sample losses
-    ref.optimizer.zero_grad()
-    l = sum(ref.loss_function(ref.model(x[i:i + 1]), y[i:i + 1]) for i in range(2)) / 2
-    l.backward(); ref.optimizer.step()
+    # mean over ranks of per-rank (batch 1) gradients == gradient of the mean of the two per-sample losses; one thread like the ranks:
+    # Adam's first step is about lr * sign(g), so a gradient at rounding level summed in another order moves its parameter by 2 lr
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        ref.optimizer.zero_grad()
+        l = sum(ref.loss_function(ref.model(x[i:i + 1]), y[i:i + 1]) for i in range(2)) / 2
+        l.backward(); ref.optimizer.step()
+    finally:
+        torch.set_num_threads(threads)
     for k, v in ref.model.state_dict().items():
         if k.startswith("skip_layers"):
             continue
@@ -227,6 +236,8 @@ def test_checkpoint_files_round_trip_and_metrics_csv(tmp_path):
 
 
 def _gan_worker(rank, world, port, outdir):
+    # a CPU rank: torch's Python-level device queries (torch.cuda.is_available(), its optimisers' too) see no GPU here, as on a CPU box
+    os.environ.update(HIP_VISIBLE_DEVICES="", PYTORCH_NVML_BASED_CUDA_CHECK="1")
     import torch.distributed as dist
     from octa_autosegmentation_amd.models.gan_seg_trainer import GanSegTrainer
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
@@ -308,7 +319,14 @@ def test_gan_seg_update_matches_the_reference_fixture(tag, idt):
     (tools/make_golden_ganseg.he_weights) -- the variant that also runs on the GPU in fp32 and through the bf16 / MFMA path
     (tests/test_models_gpu.py); with the ramp some InstanceNorm inputs are nearly constant, the generator's gradient norm is 1e6 and
     a different summation order alone moves step-2 losses by tens of percent."""
-    losses, gnorm, sums, g = run_gan_seg_fixture(tag, idt)
+    # the step-2 figures amplify rounding, so the host's core count must not choose the reduction order: with 128 threads (a 256-thread
+    # host) the segmentor's step-2 gradient norm of he_idt0 moves by 2.1e-3, with 1 or 8 threads it matches
+    threads = torch.get_num_threads()
+    torch.set_num_threads(min(threads, 8))
+    try:
+        losses, gnorm, sums, g = run_gan_seg_fixture(tag, idt)
+    finally:
+        torch.set_num_threads(threads)
     # step 0: the forward composition alone (fp32 summation order); step 1: after one Adam step of all three optimisers, where
     # first-step updates are lr * sign(g) and parameters with rounding-noise gradients move either way
     for step in range(2):

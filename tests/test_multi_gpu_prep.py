@@ -68,6 +68,8 @@ def test_host_budget_and_affinity_shares():
 
 
 def _worker(rank, world, port, out):
+    # a CPU rank: torch's Python-level device queries (torch.cuda.is_available(), its optimisers' too) see no GPU here, as on a CPU box
+    os.environ.update(HIP_VISIBLE_DEVICES="", PYTORCH_NVML_BASED_CUDA_CHECK="1")
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
                       LOCAL_WORLD_SIZE=str(world), OCTA_NO_AFFINITY="1")
@@ -97,6 +99,10 @@ def _worker(rank, world, port, out):
 
 
 def test_eight_ranks_seeds_plans_arena_and_rank_count(tmp_path):
+    if torch.cuda.is_available():
+        # torch's autograd engine asks HIP for its devices on a process's first backward pass, so on a GPU box every rank would hold
+        # the GPU open: eight ranks are more processes than a GPU may be shared by. The test runs in the CPU half of the suite.
+        pytest.skip("eight CPU ranks would each open the GPU")
     import torch.multiprocessing as mp
     from octa_autosegmentation_amd.models.segmentation_trainer import SegmentationTrainer
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()

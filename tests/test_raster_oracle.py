@@ -113,16 +113,42 @@ def test_oracle_reproduces_16_more_shipped_pairs():
         assert (octa_oracle.fs_dither(img) == label).all(), name
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/datasets/labels"), reason="reference datasets not present")
+def _decode_sample_graph(g, k):
+    """Edge array [n, 7] of graph k of raster_labels_sample_golden (tools/make_golden_raster_labels_sample.py): node coordinates as
+    printed in the CSV (mantissa * 10**exponent), a node stored as its difference to its parent at its own exponent; exact integers in
+    units of 1e-16, so every double equals float() of the CSV token."""
+    delta, x, parent, ends = g[f"delta_{k}"], g[f"exp_{k}"], g[f"parent_{k}"], g[f"ends_{k}"]
+    v = [None] * len(delta)
+    for j in range(len(delta)):
+        v[j] = [(int(d) + (v[int(parent[j])][c] // 10 ** (16 + int(e)) if parent[j] >= 0 else 0)) * 10 ** (16 + int(e))
+                for c, (d, e) in enumerate(zip(delta[j], x[j]))]
+    nodes = np.array([[float(f"{a}e-16") for a in p] for p in v])
+    return np.concatenate([nodes[ends[:, 0]], nodes[ends[:, 1]], g[f"radii_{k}"][g[f"radius_index_{k}"]][:, None]], axis=1)
+
+
 def test_oracle_reproduces_shipped_labels_sample():
-    """In the build container only: a spread of the 500 shipped csv<->label pairs."""
-    import csv
-    from PIL import Image
-    names = sorted(os.listdir("/root/reference/datasets/vessel_graphs"))[::100]
+    """A spread of the 500 shipped csv<->label pairs: every 100th of the sorted list. Two of the five are held by raster_golden.npz and
+    raster_shipped_golden.npz (edges, label bits); the other three by raster_labels_sample_golden.npz.xz (edges, SHA-256 of the
+    label's pixels). tools/make_golden_raster_labels_sample.py checks that both hold exactly the shipped files' contents."""
+    import io
+    import lzma
+    with open(os.path.join(ROOT, "tests", "golden", "raster_labels_sample_golden.npz.xz"), "rb") as f:
+        g = np.load(io.BytesIO(lzma.decompress(f.read())))
+    names = [str(n) for n in g["names"]]
+    new = [str(n) for n in g["new_names"]]
+    held = {}
+    r = np.load(os.path.join(ROOT, "tests", "golden", "raster_golden.npz"))
+    held[str(r["graph0_name"])] = (r["graph0_edges"], r["graph0_label_packed"])
+    s = np.load(os.path.join(ROOT, "tests", "golden", "raster_shipped_golden.npz"))
+    for k, n in enumerate(s["names"]):
+        held[str(n)] = (s[f"edges_{k}"], s[f"label_packed_{k}"])
+    assert len(names) == 5 and set(names) <= set(new) | set(held)
     for fn in names:
-        with open(os.path.join("/root/reference/datasets/vessel_graphs", fn), newline="") as fh:
-            rows = list(csv.DictReader(fh))
-        p = lambda s: [float(c) for c in s[1:-1].split(" ") if len(c) > 0]
-        e = np.array([p(r["node1"]) + p(r["node2"]) + [float(r["radius"])] for r in rows])
-        lab = np.array(Image.open(os.path.join("/root/reference/datasets/labels", fn[:-4] + ".png")).convert("L"))
-        assert (octa_oracle.fs_dither(octa_oracle.rasterize(e, [1216, 1216])) == lab).all(), fn
+        if fn in new:
+            k = new.index(fn)
+            lab = octa_oracle.fs_dither(octa_oracle.rasterize(_decode_sample_graph(g, k), [1216, 1216]))
+            assert hashlib.sha256(np.ascontiguousarray(lab, np.uint8).tobytes()).hexdigest() == str(g[f"label_sha256_{k}"]), fn
+        else:
+            e, bits = held[fn]
+            label = np.unpackbits(bits)[: 1216 * 1216].reshape(1216, 1216) * 255
+            assert (octa_oracle.fs_dither(octa_oracle.rasterize(e, [1216, 1216])) == label).all(), fn

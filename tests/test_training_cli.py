@@ -215,6 +215,8 @@ def test_train_test_validate_clis_and_resume(tmp_path):
 
 
 def _two_rank_train(rank, world, port, cfg_path, outfile):
+    # a CPU rank: torch's Python-level device queries (torch.cuda.is_available(), its optimisers' too) see no GPU here, as on a CPU box
+    os.environ.update(HIP_VISIBLE_DEVICES="", PYTORCH_NVML_BASED_CUDA_CHECK="1")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     import train as train_cli
     run = train_cli.main(["--config_file", cfg_path, "--num_workers", "0"])

@@ -2,7 +2,6 @@
 slower when more workgroups than one launch's share the GPU.   python tools/time_sim_concurrent.py [K=4] [B=128]"""
 import os, sys, time, threading
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 from octa_autosegmentation_amd.utils import configs
 from octa_autosegmentation_amd.vessel_graph_generation import greenhouse
