@@ -341,6 +341,24 @@ int octa_conv2d_f32_nchw(octa_ctx *ctx, const float *d_x, const float *d_wp, con
 int octa_convtranspose2x2_f32_nchw(octa_ctx *ctx, const float *d_x, const float *d_wp, float *d_y, int N, int Cin, int H, int W, int Cout,
                                    void *stream);
 
+/* Data gradient of an fp32 layer on the same matrix-core kernel (exact fp32): d_dx [N][Cin][H][W] (overwritten) from d_dy
+ * [N][Cout][Ho][Wo]. Layers: Conv2d k/stride/pad 1/1/0, 3/1/1, 3/2/1 (transposed = 0) and ConvTranspose2d k = stride in {1, 2}, pad 0
+ * (transposed = 1, Ho = k H). d_wd: the layer's weights in the data-gradient layout -- stride 1: [Cout][K*K][Cin] with flipped taps;
+ * 3x3 stride 2: [4 output parities][Cout][4 taps][Cin], one sub-kernel per parity class, no zero-inserted dy; transposed:
+ * [Cout][k*k][Cin] (csrc/conv_f32.hip spells the layouts out). */
+int octa_conv2d_f32_dgrad_nchw(octa_ctx *ctx, const float *d_dy, const float *d_wd, float *d_dx, int N, int Cin, int H, int W, int Cout,
+                               int K, int stride, int pad, int Ho, int Wo, int transposed, void *stream);
+
+/* *bytes = the size of the workspace octa_conv2d_f32_wgrad_nchw needs for this shape (a function of the shape only). */
+int octa_conv2d_f32_wgrad_workspace(int N, int Cin, int H, int W, int Cout, int K, int stride, int pad, int Ho, int Wo, size_t *bytes);
+
+/* Weight gradient of an fp32 layer, exact fp32 on the matrix cores and deterministic (per-chunk partials in the caller's workspace
+ * d_ws, added in a fixed order; no atomics): d_dw [Cout][Cin][K][K] = sum over n and output pixels of
+ * d_dy[n][co][oy][ox] * d_x[n][ci][oy stride + r - pad][ox stride + s - pad]; d_db [Cout] = sum of d_dy, or NULL. Both overwritten.
+ * K / stride in {1/1, 3/1, 3/2, 2/2}. A transposed layer passes its dy as d_x and its x as d_dy. */
+int octa_conv2d_f32_wgrad_nchw(octa_ctx *ctx, const float *d_x, const float *d_dy, float *d_dw, float *d_db, void *d_ws, size_t ws_bytes, int N,
+                               int Cin, int H, int W, int Cout, int K, int stride, int pad, int Ho, int Wo, void *stream);
+
 /* 4x4 convolution, stride 1, zero padding `pad`, on the same DMA-staged MFMA kernel (KS = 4 instantiation): the inner
  * layers of the 70x70 PatchGAN (models/networks.py:445-500 NLayerDiscriminator: Conv2d(ndf*m, ndf*2m, 4, 1, 1)).
  * d_x [N][H][W][Cin] bf16, d_w [16][Cout][Cin] bf16 (tap 4r+s), d_y [N][H+2pad-3][W+2pad-3][Cout] bf16; Cin, Cout

@@ -74,6 +74,9 @@ SIGNATURES = {
     "octa_sim_is_large": (c_int, [c_void_p]),
     "octa_conv2d_f32_nchw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 14 + [c_void_p]),
     "octa_convtranspose2x2_f32_nchw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "octa_conv2d_f32_dgrad_nchw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 11 + [c_void_p]),
+    "octa_conv2d_f32_wgrad_workspace": (c_int, [c_int] * 10 + [ctypes.POINTER(c_size_t)]),
+    "octa_conv2d_f32_wgrad_nchw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t] + [c_int] * 10 + [c_void_p]),
     "octa_sim_fields": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, ctypes.c_int64, c_void_p]),
     "octa_instnorm_lrelu_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p]),
     "octa_instnorm_lrelu_nhwc_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, c_void_p]),

@@ -25,7 +25,7 @@ USE_FUSED_NORM = True
 # CUDA inputs run channels-last in bf16 through the hand-written MFMA convolution (csrc/conv.hip) and the NHWC
 # norm kernels; False = torch/MIOpen modules (the fp32 reference path of the parity tests)
 USE_MFMA_CONV = True
-USE_F32_MFMA = True      # fp32 forward passes that record no gradient run csrc/conv_f32.hip (exact-fp32 MFMA) instead of the vendor library
+USE_F32_MFMA = True      # fp32 passes run csrc/conv_f32.hip (exact-fp32 MFMA) instead of the vendor library; with USE_MFMA_CONV also the ones that record gradients
 # normalise-on-load (the normalised activations never go to HBM: models/mfma_conv.py) is implemented and tested but
 # measured SLOWER on MI355X (37.5 vs 31.9 ms per step): every output-channel block of a layer re-stages and
 # re-normalises the same input tile, which costs more VALU work than the two HBM passes it saves
@@ -49,7 +49,9 @@ import collections as _collections
 import contextlib as _contextlib
 import warnings as _warnings
 
-PATH_COUNTS = _collections.Counter()     # 'mfma' (bf16 NHWC passes), 'f32_mfma' (exact-fp32 convolutions), 'vendor' (fallbacks)
+# 'mfma' (bf16 NHWC passes), 'f32_mfma' (gradient-free exact-fp32 convolutions), 'f32_train' (grad-recording exact-fp32 convolutions:
+# conv_f32.ConvF32Train), 'vendor' (fallbacks)
+PATH_COUNTS = _collections.Counter()
 _WARNED = set()
 _REFERENCE_DEPTH = [0]
 
@@ -83,7 +85,8 @@ def _vendor_fallback(where, why):
 
 def _why_not_own_kernels(c, x):
     if x.dtype == torch.float32 and torch.is_grad_enabled() and (x.requires_grad or c.weight.requires_grad):
-        return "fp32 pass that records gradients (the exact-fp32 MFMA kernels are forward-only; train with General.amp: true)"
+        return ("fp32 pass that records gradients on a layer outside the exact-fp32 gradient kernels (Conv2d 1x1, 3x3 stride 1 / 2; "
+                "ConvTranspose2d 1x1, 2x2 stride 2 without bias)")
     if x.dtype == torch.float32:
         return "fp32 layer shape outside csrc/conv_f32.hip (kernel/stride 1/1, 3/1, 3/2, 4/1, 7/1, transposed 1/1, 2/2)"
     return f"{x.dtype} modules path: the bf16 NHWC path did not apply ({_LAST_MFMA_REFUSAL[0] or 'not a bf16 / bf16-autocast pass'})"
@@ -112,6 +115,11 @@ class _Conv(nn.Module):
             if conv_f32.applies(c, x):
                 PATH_COUNTS['f32_mfma'] += 1
                 return conv_f32.forward(c, x)
+            # fp32 training (General.amp: false): forward and both gradients on the exact-fp32 kernels. The torch modules stay the
+            # reference of the parity tests (vendor_reference() / USE_MFMA_CONV = False).
+            if USE_MFMA_CONV and _REFERENCE_DEPTH[0] == 0 and conv_f32.trainable(c, x):
+                PATH_COUNTS['f32_train'] += 1
+                return conv_f32.train_forward(c, x)
         if x.is_cuda:
             _vendor_fallback(f"DynUNet {type(c).__name__}({c.in_channels}->{c.out_channels}, k{c.kernel_size[0]}, s{c.stride[0]})",
                              _why_not_own_kernels(c, x))
@@ -504,7 +512,7 @@ class ResnetGenerator(nn.Module):
                 PATH_COUNTS['f32'] = PATH_COUNTS.get('f32', 0) + 1
                 return _run_f32(list(self.model), x, "ResnetGenerator")
             if x.is_cuda:
-                _vendor_fallback("ResnetGenerator", f"{x.dtype} pass that is neither bf16 autocast nor gradient-free fp32 (the exact-fp32 MFMA kernels are forward-only)")
+                _vendor_fallback("ResnetGenerator", f"{x.dtype} pass that is neither bf16 autocast nor gradient-free fp32 (the exact-fp32 gradient kernels cover the DynUNet layer kinds only)")
             return self.model(x)
         PATH_COUNTS['mfma'] += 1
         from . import mfma_conv as mc
@@ -583,7 +591,7 @@ class NLayerDiscriminator(nn.Module):
                 PATH_COUNTS['f32'] = PATH_COUNTS.get('f32', 0) + 1
                 return _run_f32(list(self.model), x, "NLayerDiscriminator")
             if x.is_cuda:
-                _vendor_fallback("NLayerDiscriminator", f"{x.dtype} pass that is neither bf16 autocast nor gradient-free fp32 (the exact-fp32 MFMA kernels are forward-only)")
+                _vendor_fallback("NLayerDiscriminator", f"{x.dtype} pass that is neither bf16 autocast nor gradient-free fp32 (the exact-fp32 gradient kernels cover the DynUNet layer kinds only)")
             return self.model(x)
         PATH_COUNTS['mfma'] += 1
         from . import mfma_conv as mc
