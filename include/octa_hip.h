@@ -625,6 +625,10 @@ int octa_sim_trace(octa_sim *sim, int32_t *h_trace);
  * 4 O2->CO2, 6 assign-ven, 7 speculate-ven, 8 ordered-ven, 9 CO2 removal), then 8 timers of the kd-order build. */
 int octa_sim_stats(octa_sim *sim, int64_t *h_stats);
 
+/* How the O2 -> CO2 conversions of the last run ordered their CPython set, h_paths[B][2] int64: conversions whose table was certified
+ * the same for every order of the cKDTree query results (no kd order built), conversions that built the kd order. */
+int octa_sim_kd_paths(octa_sim *sim, int64_t *h_paths);
+
 /* When each sample held a CU (persistent form): h_spans[B][2] = the GPU's 100 MHz wall clock when a workgroup first took the sample
  * and when it last left it. The clock is common to all launches on the device, so spans of concurrent launches can be laid over
  * each other: sum of spans / (CUs x window) = the share of CU time the simulator used (bench.py's cu_time_used). */

@@ -45,6 +45,7 @@ using namespace OCTA_SIMK;
 #define octa_sim_export_edges_device OCTA_SIM_FN(export_edges_device)
 #define octa_sim_trace OCTA_SIM_FN(trace)
 #define octa_sim_stats OCTA_SIM_FN(stats)
+#define octa_sim_kd_paths OCTA_SIM_FN(kd_paths)
 #define octa_sim_fields OCTA_SIM_FN(fields)
 #define octa_sim_service_stats OCTA_SIM_FN(service_stats)
 #define octa_sim_geometry OCTA_SIM_FN(geometry)
@@ -1393,6 +1394,12 @@ extern "C" int octa_sim_stats(OCTA_SIM_T *S, int64_t *h_stats) {
         for (int k = 0; k < 16; k++) o[8 + k] = sc.prof[k];
         for (int k = 0; k < 8; k++) o[24 + k] = sc.kdprof[k];
     }
+    return 0;
+}
+
+extern "C" int octa_sim_kd_paths(OCTA_SIM_T *S, int64_t *h_paths) {
+    if (!S || !S->ran || !h_paths) { octa::set_error("octa_sim_kd_paths: run the simulation first"); return -2; }
+    for (int s = 0; s < S->B; s++) { h_paths[2 * s] = S->h_sc[s].kd_path[0]; h_paths[2 * s + 1] = S->h_sc[s].kd_path[1]; }
     return 0;
 }
 

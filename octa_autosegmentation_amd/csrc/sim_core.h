@@ -161,6 +161,7 @@ struct SampleScalars {
     long respec;
     long prof[16];  // accumulated 100 MHz ticks per phase (thread 0), see sim.hip
     long kdprof[8]; // kd_build breakdown: bbox, dim, gather, nth(wave), nth(thread), next-level, finalize
+    int kd_path[2]; // O2 -> CO2 conversions whose set order was certified without the kd order / that built it (phase_satisfy_art)
     // persistent form (sim.hip): a workgroup whose host answer does not arrive in time PARKS -- it records where to resume and
     // leaves the kernel; the host serves it at the kernel boundary and launches again
     int resume_it, resume_stage;   // stage 0: top of iteration resume_it; 1: behind its arterial mailbox
@@ -627,6 +628,57 @@ OCTA_HD inline void pyset_add(PySetView &s, int key, unsigned long long hash) {
         } while (probes--);
         perturb >>= 5;
         i = (i * 5 + 1 + perturb) & (unsigned long long)s.mask;
+    }
+}
+
+// Is the table of a set that only grows the same for EVERY order of its keys inside their groups? The D distinct keys arrive in groups
+// (arrival p: key dk[p], hash hashes[dk[p]], group dg[p]; groups non-decreasing), the order inside a group being provisional. Certified when
+//   - no same-group blocker: in every table generation, each slot a key's probe sequence passes before its own slot is held by a key of an
+//     earlier group or by an entry re-inserted from the previous generation, and
+//   - no straddled resize: the key whose insertion resizes the table is the last of its group.
+// Then, group by group, each key lands on the first slot of its sequence that earlier groups do not hold, whatever the order inside its
+// group, and a resize re-inserts a table that is fixed already. Sequential form (one thread); the parallel replay of phase_satisfy_art
+// makes the same checks on its priority tables. own: [s_max] ints, ord0 / ord1: [D] ints. false also when a table would exceed s_max.
+OCTA_HD inline bool pyset_order_free(const int *dk, const int *dg, const unsigned long long *hashes, int D, int *own, int *ord0, int *ord1,
+                                     int s_max) {
+    int S = 8, n_prev = 0;
+    int *ord = ord0, *ord_next = ord1;
+    while (true) {
+        const int thr = (3 * (S - 1) + 4) / 5;            // the insertion that makes fill * 5 >= mask * 3 resizes the table
+        const int upto = D < thr ? D : thr;
+        const unsigned long long mask = (unsigned long long)(S - 1);
+        for (int p = n_prev; p < upto; p++) ord[p] = p;   // behind the re-inserted entries: the arrivals, in order
+        for (int e = 0; e < S; e++) own[e] = -1;
+        for (int p = 0; p < upto; p++) {
+            const int k = ord[p];
+            const unsigned long long hsh = hashes[dk[k]];
+            unsigned long long perturb = hsh, i = hsh & mask;
+            while (true) {
+                unsigned long long e = i;
+                int probes = (i + 9 <= mask) ? 9 : 0;
+                bool placed = false;
+                do {
+                    const int q = own[e];
+                    if (q < 0) { own[e] = p; placed = true; break; }
+                    if (p >= n_prev && q >= n_prev && dg[q] == dg[k]) return false;    // (ord[q] = q behind the re-inserted entries)
+                    e++;
+                } while (probes--);
+                if (placed) break;
+                perturb >>= 5;
+                i = (i * 5 + 1 + perturb) & mask;
+            }
+        }
+        if (D < thr) return true;
+        if (D > thr && dg[thr - 1] == dg[thr]) return false;
+        const int minused = upto > 50000 ? upto * 2 : upto * 4;
+        int newS = 8;
+        while (newS <= minused) newS <<= 1;
+        if (newS > s_max) return false;
+        int c = 0;
+        for (int e = 0; e < S; e++) if (own[e] >= 0) ord_next[c++] = ord[own[e]];   // re-insertion in the old table's slot order
+        { int *t = ord; ord = ord_next; ord_next = t; }
+        n_prev = upto;
+        S = newS;
     }
 }
 
@@ -3226,8 +3278,8 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
     const double ek = P.eps_k, ek2 = ek * ek;
     long t0 = OCTA_SUBPROF_T0();
     for (int i = b.tid; i < n_oxy; i += b.nth) A.removed[i] = 0;
-    int *ctl = b.coll() + 100;
-    if (b.tid == 0) ctl[0] = 0;
+    int *ctl = b.coll() + 100;         // [0] hit pairs, [1] set when the certificate of the provisional order fails (step 5)
+    if (b.tid == 0) { ctl[0] = 0; ctl[1] = 0; }
     b.sync();
     // 1. (new node, sink) hits from a grid over the new nodes: raw pairs node_local << 14 | sink
     {
@@ -3253,18 +3305,7 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
     if (n_new > (1 << (32 - IDX_BITS))) { if (b.tid == 0) atomic_or_int(&sc->err, ERR_PAIR_CAP); }
     b.sync();
     if (n_pairs == 0) return;  // nothing satisfied: no conversion, no deletion (uniform across the block)
-    // 2. cKDTree order of the O2 list, only as deep as the hit sinks need it; pairs get kd ranks
-    kd_build(b, A.oxy, n_oxy, A.kd_idx, A.kd_rank, reinterpret_cast<float *>(A.hashes) /* free until step 3 */, 0.0, zext, sc->kdprof, A.removed, true);
-#if OCTA_SIM_DUP & 1
-    kd_build(b, A.oxy, n_oxy, A.kd_idx, A.kd_rank, reinterpret_cast<float *>(A.hashes), 0.0, zext, nullptr, A.removed, true);
-#endif
-    for (int i = b.tid; i < n_pairs; i += b.nth) {
-        unsigned pr = A.pairs[i];
-        A.pairs[i] = (pr & ~IDX_MASK) | (unsigned)A.kd_rank[pr & IDX_MASK];
-    }
-    b.sync();
-    OCTA_SUBPROF(sc, 11, t0);
-    // 3. venous proximity + tuple hash for every removed sink. Inverted like the candidate tests (round 3): the grid holds the few
+    // 2. venous proximity + tuple hash for every removed sink. Inverted like the candidate tests (round 3): the grid holds the few
     //    hundred removed sinks, every venous node visits the cells around itself and flags the sinks within eps_k (same expression,
     //    same operand order; an existence test). Round 2 binned all ~13 k venous nodes per iteration for these few hundred queries.
     {
@@ -3305,240 +3346,299 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
         b.sync();
     }
     OCTA_SUBPROF(sc, 12, t0);
-    // 4. sort the pairs: new nodes in order, hits in cKDTree order
-    unsigned *keys = reinterpret_cast<unsigned *>(b.user_of<32>());
-    int n_pow2 = 1;
-    while (n_pow2 < n_pairs) n_pow2 <<= 1;
-    for (int i = b.tid; i < n_pow2; i += b.nth) keys[i] = i < n_pairs ? A.pairs[i] : 0xffffffffu;
-    b.sync();
-    if (n_pairs > 0) blk_sort_u32(b, keys, n_pow2);
-    for (int i = b.tid; i < n_pairs; i += b.nth) A.pairs[i] = keys[i];
-    b.sync();
-    OCTA_SUBPROF(sc, 13, t0);
-    // 5. CPython set insertion order -> CO2 append order
-    bool set_in_lds = false;
+    // The cKDTree order of a node's hits is observed only through the order in which they enter the CPython set `to_add`, and a
+    // set's table depends on its insertion order only where keys contend for slots. A sink enters with the first new node that hits
+    // it (its group): the order across groups is the node order, known without a tree. Pass 0 inserts each group's sinks in index
+    // order and certifies that no order inside a group could change the table (pyset_order_free); only where that fails does pass 1
+    // build the kd order and replay the exact insertion order (45 % of the builds certify).
+    bool set_in_lds = false, ranked = false;
 #ifdef OCTA_SIM_DEBUG_SAT
     int dbg_n_ins = -1, dbg_mask = -1, dbg_base = -1;
     const int dbg_n_co2_in = sc->n_co2;
 #endif
+    for (int pass = 0; pass < 2; pass++) {
+        ranked = pass > 0;
+        if (ranked) {
+            // 3. cKDTree order of the O2 list, only as deep as the hit sinks need it; pairs get kd ranks
+            kd_build(b, A.oxy, n_oxy, A.kd_idx, A.kd_rank, reinterpret_cast<float *>(A.tmp_dbl), 0.0, zext, sc->kdprof, A.removed, true);
+#if OCTA_SIM_DUP & 1
+            kd_build(b, A.oxy, n_oxy, A.kd_idx, A.kd_rank, reinterpret_cast<float *>(A.tmp_dbl), 0.0, zext, nullptr, A.removed, true);
+#endif
+            for (int i = b.tid; i < n_pairs; i += b.nth) {
+                unsigned pr = A.pairs[i];
+                A.pairs[i] = (pr & ~IDX_MASK) | (unsigned)A.kd_rank[pr & IDX_MASK];
+            }
+            b.sync();
+            OCTA_SUBPROF(sc, 11, t0);
+        }
+        // 4. sort the pairs: new nodes in order, hits in sink order (pass 0) or cKDTree order (pass 1)
+        unsigned *keys = reinterpret_cast<unsigned *>(b.user_of<32>());
+        int n_pow2 = 1;
+        while (n_pow2 < n_pairs) n_pow2 <<= 1;
+        for (int i = b.tid; i < n_pow2; i += b.nth) keys[i] = i < n_pairs ? A.pairs[i] : 0xffffffffu;
+        b.sync();
+        if (n_pairs > 0) blk_sort_u32(b, keys, n_pow2);
+        for (int i = b.tid; i < n_pairs; i += b.nth) A.pairs[i] = keys[i];
+        b.sync();
+        OCTA_SUBPROF(sc, 13, t0);
+        // 5. CPython set insertion order -> CO2 append order
 #if defined(__HIP_DEVICE_COMPILE__)
-    // Usual case (<= LSET_PAIRS hits): the insert stream (sink, hash) is compacted into the table area in parallel and the set is
-    // replayed there by the WHOLE workgroup (round 4; one wave inserting key after key until then: 21 ms per sample, the other three
-    // waves idle). What makes a parallel replay possible: a CPython set that only grows never moves an entry inside one table, so
-    // the slot of the k-th distinct key is the first slot of ITS probe sequence that no earlier key of the same table holds -- a
-    // fixed point that insertion with priorities computes in any order (a key that finds a slot held by a later key takes it and
-    // carries the displaced key on along that key's own sequence). A resize re-inserts the entries in the old table's slot order,
-    // which is the same operation with the old slot as the priority. The resizes happen at fixed counts of distinct keys
-    // (5, 19, 77, 307, ... -> 32, 128, 512, 2048 slots), so the replay is one priority insertion per table generation:
-    //   fp[OCAP]: first arrival of a sink (duplicates of a key never touch the table), later own[slot] = priority of the slot's entry,
-    //   at the end the slot's key (-1: empty) -- the table the read-out below walks;
-    //   in_key / in_hash: arrivals; dk / dh: distinct keys in arrival order; ord0 / ord1: entry of a priority (this / next generation).
+        // Usual case (<= LSET_PAIRS hits): the insert stream (sink, hash) is compacted into the table area in parallel and the set is
+        // replayed there by the WHOLE workgroup (round 4; one wave inserting key after key until then: 21 ms per sample, the other three
+        // waves idle). What makes a parallel replay possible: a CPython set that only grows never moves an entry inside one table, so
+        // the slot of the k-th distinct key is the first slot of ITS probe sequence that no earlier key of the same table holds -- a
+        // fixed point that insertion with priorities computes in any order (a key that finds a slot held by a later key takes it and
+        // carries the displaced key on along that key's own sequence). A resize re-inserts the entries in the old table's slot order,
+        // which is the same operation with the old slot as the priority. The resizes happen at fixed counts of distinct keys
+        // (5, 19, 77, 307, ... -> 32, 128, 512, 2048 slots), so the replay is one priority insertion per table generation:
+        //   fp[OCAP]: first arrival of a sink (duplicates of a key never touch the table), later own[slot] = priority of the slot's entry,
+        //   at the end the slot's key (-1: empty) -- the table the read-out below walks;
+        //   in_key / in_hash: arrivals; dk / dh: distinct keys in arrival order; ord0 / ord1: entry of a priority (this / next generation).
+        // in_key and dk hold node << IDX_BITS | sink: the node of a key's first arrival is its group, which the certificate of pass 0 compares.
 #if defined(OCTA_SIM_PROF_SET)
-    // diagnostic build: the kd slots of the phase profile hold the steps of the set replay: insert stream, distinct keys, generations,
-    // key table, read-out
-    long _pt = (long)wall_clock64();
+        // diagnostic build: the kd slots of the phase profile hold the steps of the set replay: insert stream, distinct keys, generations,
+        // key table, read-out
+        long _pt = (long)wall_clock64();
 #define PSP(slot) do { if (b.tid == 0) { long _t = (long)wall_clock64(); sc->kdprof[slot] += _t - _pt; _pt = _t; } } while (0)
 #else
 #define PSP(slot) do { } while (0)
 #endif
-    constexpr int EMPTY = 0x7fffffff;
-    // own: [max(OCAP, s_max)] ints; in_key / in_hash: [n_pairs]; dk / dh / ord0 / ord1: [number of distinct sinks]. Returns the table's mask;
-    // own[slot] then holds the slot's key (-1: empty).
-    auto replay = [&](int *own, int *in_key, unsigned long long *in_hash, int *dk, unsigned long long *dh, int *ord0, int *ord1,
-                      const int s_max) __attribute__((always_inline)) -> int {
-        int n_ins = 0;
-        for (int p0 = 0; p0 < n_pairs; p0 += b.nth) {          // ordered compaction of the insert stream, b.nth pairs per round
-            const int i = p0 + b.tid;
-            int o = -1, take = 0;
-            unsigned long long hsh = 0;
-            if (i < n_pairs) {
-                o = (int)A.kd_idx[keys[i] & IDX_MASK];         // the sorted pairs are still in the LDS
-                take = A.ven_near[o] ? 0 : 1;
-                hsh = A.hashes[o];                             // fetched beside the flag, not behind it
-            }
-            int ex;
-            const int tot = blk_scan(b, take, &ex);
-            if (take) { in_key[n_ins + ex] = o; in_hash[n_ins + ex] = hsh; }
-            n_ins += tot;
-        }
-        b.sync();
-        PSP(0);
-        // distinct keys in arrival order
-        for (int i = b.tid; i < n_ins; i += b.nth) own[in_key[i]] = EMPTY;
-        b.sync();
-        for (int i = b.tid; i < n_ins; i += b.nth) atomic_min_int(&own[in_key[i]], i);
-        b.sync();
-        int D = 0;
-        for (int p0 = 0; p0 < n_ins; p0 += b.nth) {
-            const int i = p0 + b.tid;
-            const bool first = i < n_ins && own[in_key[i]] == i;
-            int ex;
-            const int tot = blk_scan(b, first ? 1 : 0, &ex);
-            if (first) { dk[D + ex] = in_key[i]; dh[D + ex] = in_hash[i]; }
-            D += tot;
-        }
-        b.sync();
-        PSP(1);
-        // one priority insertion per table generation
-        int S = 8, n_prev = 0;
-        int *ord = ord0, *ord_next = ord1;
-        while (true) {
-            const int thr = (3 * (S - 1) + 4) / 5;            // the insertion that makes fill * 5 >= mask * 3 resizes the table
-            const int upto = D < thr ? D : thr;               // distinct keys of this generation's table
-            const unsigned long long mask = (unsigned long long)(S - 1);
-            for (int p = n_prev + b.tid; p < upto; p += b.nth) ord[p] = p;      // behind the re-inserted entries: the arrivals, in order
-            for (int e = b.tid; e < S; e += b.nth) own[e] = EMPTY;
-            b.sync();
-            for (int p = b.tid; p < upto; p += b.nth) {
-                int cur = p;
-                // CPython's probe sequence: slot i, then up to nine slots behind it (if they fit), then i = 5 i + 1 + (perturb >>= 5)
-                unsigned long long hsh = dh[ord[cur]], i = hsh & mask, perturb = hsh;
-                int lin = 0, nlin = (i + 9 <= mask) ? 9 : 0;
-                auto next = [&] {
-                    if (lin < nlin) { lin++; return; }
-                    perturb >>= 5;
-                    i = (i * 5 + 1 + perturb) & mask;
-                    nlin = (i + 9 <= mask) ? 9 : 0; lin = 0;
-                };
-                while (true) {
-                    const int slot = (int)i + lin;
-                    const int old = atomic_min_ret_int(&own[slot], cur);
-                    if (old == EMPTY) break;                  // an empty slot: placed
-                    if (old > cur) {                          // a later entry held it: it moves on along ITS sequence, from behind this slot
-                        cur = old;
-                        hsh = dh[ord[cur]]; i = hsh & mask; perturb = hsh; lin = 0; nlin = (i + 9 <= mask) ? 9 : 0;
-                        while ((int)i + lin != slot) next();  // (its first visit of the slot is the one it was placed by)
-                    }
-                    next();
+        constexpr int EMPTY = 0x7fffffff;
+        // own: [max(OCAP, s_max)] ints; in_key / in_hash: [n_pairs]; dk / dh / ord0 / ord1: [number of distinct sinks]. Returns the table's mask;
+        // own[slot] then holds the slot's key (-1: empty).
+        auto replay = [&](int *own, int *in_key, unsigned long long *in_hash, int *dk, unsigned long long *dh, int *ord0, int *ord1,
+                          const int s_max) __attribute__((always_inline)) -> int {
+            int n_ins = 0;
+            for (int p0 = 0; p0 < n_pairs; p0 += b.nth) {          // ordered compaction of the insert stream, b.nth pairs per round
+                const int i = p0 + b.tid;
+                int o = -1, take = 0;
+                unsigned long long hsh = 0;
+                if (i < n_pairs) {
+                    o = ranked ? (int)A.kd_idx[keys[i] & IDX_MASK] : (int)(keys[i] & IDX_MASK);   // the sorted pairs are still in the LDS
+                    take = A.ven_near[o] ? 0 : 1;
+                    hsh = A.hashes[o];                             // fetched beside the flag, not behind it
                 }
-            }
-            b.sync();
-            if (D < thr) break;                               // no resize behind this generation: its table is the set
-            const int minused = upto > 50000 ? upto * 2 : upto * 4;
-            int newS = 8;
-            while (newS <= minused) newS <<= 1;
-            if (newS > s_max) { if (b.tid == 0) atomic_or_int(&sc->err, ERR_SET_CAP); break; }
-            // the entries in slot order = the priorities of the re-insertion
-            {
-                const int lane = b.tid & 63, wv = b.tid >> 6, nw = (b.nth + 63) >> 6;
-                const int seg = ((S + nw * 64 - 1) / (nw * 64)) * 64;
-                const int s0 = wv * seg < S ? wv * seg : S, s1 = s0 + seg < S ? s0 + seg : S;
-                int c = 0;
-                for (int e0 = s0; e0 < s1; e0 += 64) c += (int)__popcll(__ballot(e0 + lane < s1 && own[e0 + lane] != EMPTY));
                 int ex;
-                blk_scan(b, lane == 0 ? c : 0, &ex);
-                int at = __builtin_amdgcn_readfirstlane(ex);
-                for (int e0 = s0; e0 < s1; e0 += 64) {
-                    const int pr = e0 + lane < s1 ? own[e0 + lane] : EMPTY;
-                    const unsigned long long m = __ballot(pr != EMPTY);
-                    if (pr != EMPTY) ord_next[at + (int)__popcll(m & ((1ull << lane) - 1ull))] = ord[pr];
-                    at += (int)__popcll(m);
+                const int tot = blk_scan(b, take, &ex);
+                if (take) { in_key[n_ins + ex] = (int)((keys[i] & ~IDX_MASK) | (unsigned)o); in_hash[n_ins + ex] = hsh; }
+                n_ins += tot;
+            }
+            b.sync();
+            PSP(0);
+            // distinct keys in arrival order
+            for (int i = b.tid; i < n_ins; i += b.nth) own[(unsigned)in_key[i] & IDX_MASK] = EMPTY;
+            b.sync();
+            for (int i = b.tid; i < n_ins; i += b.nth) atomic_min_int(&own[(unsigned)in_key[i] & IDX_MASK], i);
+            b.sync();
+            int D = 0;
+            for (int p0 = 0; p0 < n_ins; p0 += b.nth) {
+                const int i = p0 + b.tid;
+                const bool first = i < n_ins && own[(unsigned)in_key[i] & IDX_MASK] == i;
+                int ex;
+                const int tot = blk_scan(b, first ? 1 : 0, &ex);
+                if (first) { dk[D + ex] = in_key[i]; dh[D + ex] = in_hash[i]; }
+                D += tot;
+            }
+            b.sync();
+            PSP(1);
+            // one priority insertion per table generation
+            int S = 8, n_prev = 0;
+            int *ord = ord0, *ord_next = ord1;
+            while (true) {
+                const int thr = (3 * (S - 1) + 4) / 5;            // the insertion that makes fill * 5 >= mask * 3 resizes the table
+                const int upto = D < thr ? D : thr;               // distinct keys of this generation's table
+                const unsigned long long mask = (unsigned long long)(S - 1);
+                for (int p = n_prev + b.tid; p < upto; p += b.nth) ord[p] = p;      // behind the re-inserted entries: the arrivals, in order
+                for (int e = b.tid; e < S; e += b.nth) own[e] = EMPTY;
+                b.sync();
+                for (int p = b.tid; p < upto; p += b.nth) {
+                    int cur = p;
+                    // CPython's probe sequence: slot i, then up to nine slots behind it (if they fit), then i = 5 i + 1 + (perturb >>= 5)
+                    unsigned long long hsh = dh[ord[cur]], i = hsh & mask, perturb = hsh;
+                    int lin = 0, nlin = (i + 9 <= mask) ? 9 : 0;
+                    auto next = [&] {
+                        if (lin < nlin) { lin++; return; }
+                        perturb >>= 5;
+                        i = (i * 5 + 1 + perturb) & mask;
+                        nlin = (i + 9 <= mask) ? 9 : 0; lin = 0;
+                    };
+                    while (true) {
+                        const int slot = (int)i + lin;
+                        const int old = atomic_min_ret_int(&own[slot], cur);
+                        if (old == EMPTY) break;                  // an empty slot: placed
+                        if (old > cur) {                          // a later entry held it: it moves on along ITS sequence, from behind this slot
+                            cur = old;
+                            hsh = dh[ord[cur]]; i = hsh & mask; perturb = hsh; lin = 0; nlin = (i + 9 <= mask) ? 9 : 0;
+                            while ((int)i + lin != slot) next();  // (its first visit of the slot is the one it was placed by)
+                        }
+                        next();
+                    }
+                }
+                b.sync();
+                if (!ranked) {
+                    // pass 0's certificate (pyset_order_free): every slot a new key passes before its own is held by a re-inserted entry or
+                    // by a key of an earlier group; the key that resizes the table is the last of its group. ord[p] = p behind n_prev.
+                    for (int p = n_prev + b.tid; p < upto; p += b.nth) {
+                        const unsigned g = (unsigned)dk[p] >> IDX_BITS;
+                        const unsigned long long hsh = dh[p];
+                        unsigned long long i = hsh & mask, perturb = hsh;
+                        int lin = 0, nlin = (i + 9 <= mask) ? 9 : 0;
+                        while (true) {
+                            const int q = own[(int)i + lin];
+                            if (q == p) break;
+                            if (q == EMPTY) { atomic_or_int(&ctl[1], 1); break; }      // (not reached: the slots in front of a key's own are held)
+                            if (q >= n_prev && ((unsigned)dk[q] >> IDX_BITS) == g) { atomic_or_int(&ctl[1], 1); break; }
+                            if (lin < nlin) { lin++; continue; }
+                            perturb >>= 5;
+                            i = (i * 5 + 1 + perturb) & mask;
+                            nlin = (i + 9 <= mask) ? 9 : 0; lin = 0;
+                        }
+                    }
+                    if (b.tid == 0 && D > thr && ((unsigned)dk[thr - 1] >> IDX_BITS) == ((unsigned)dk[thr] >> IDX_BITS)) atomic_or_int(&ctl[1], 1);
+                    b.sync();
+                    if (ctl[1]) break;                            // (uniform) pass 1 replays the exact order
+                }
+                if (D < thr) break;                               // no resize behind this generation: its table is the set
+                const int minused = upto > 50000 ? upto * 2 : upto * 4;
+                int newS = 8;
+                while (newS <= minused) newS <<= 1;
+                if (newS > s_max) { if (b.tid == 0) atomic_or_int(&sc->err, ERR_SET_CAP); break; }
+                // the entries in slot order = the priorities of the re-insertion
+                {
+                    const int lane = b.tid & 63, wv = b.tid >> 6, nw = (b.nth + 63) >> 6;
+                    const int seg = ((S + nw * 64 - 1) / (nw * 64)) * 64;
+                    const int s0 = wv * seg < S ? wv * seg : S, s1 = s0 + seg < S ? s0 + seg : S;
+                    int c = 0;
+                    for (int e0 = s0; e0 < s1; e0 += 64) c += (int)__popcll(__ballot(e0 + lane < s1 && own[e0 + lane] != EMPTY));
+                    int ex;
+                    blk_scan(b, lane == 0 ? c : 0, &ex);
+                    int at = __builtin_amdgcn_readfirstlane(ex);
+                    for (int e0 = s0; e0 < s1; e0 += 64) {
+                        const int pr = e0 + lane < s1 ? own[e0 + lane] : EMPTY;
+                        const unsigned long long m = __ballot(pr != EMPTY);
+                        if (pr != EMPTY) ord_next[at + (int)__popcll(m & ((1ull << lane) - 1ull))] = ord[pr];
+                        at += (int)__popcll(m);
+                    }
+                }
+                b.sync();
+                { int *t = ord; ord = ord_next; ord_next = t; }
+                n_prev = upto;
+                S = newS;
+            }
+            PSP(2);
+            for (int e = b.tid; e < S; e += b.nth) { const int pr = own[e]; own[e] = pr == EMPTY ? -1 : (int)((unsigned)dk[ord[pr]] & IDX_MASK); }
+            b.sync();
+            PSP(3);
+#ifdef OCTA_SIM_DEBUG_SAT
+            dbg_n_ins = n_ins;
+#endif
+            return S - 1;
+        };
+        // the tables of the replay: in the table area for the usual <= LSET_PAIRS hits; in the sample's HBM scratch for the few iterations
+        // with more (the first iteration of a mode runs with the mode's raw radii: thousands of hits -- replayed by ONE thread until
+        // round 4, 16 of the 21 ms per sample this step took)
+        constexpr bool HBM_REPLAY = (size_t)PCAP + OCAP <= (size_t)OCAP + 2 * (size_t)NCANDCAP && (size_t)OCAP * 2 <= (size_t)OCAP * 3
+                                    && PCAP <= SETCAP && OCAP <= SETCAP;
+        const int *t_key = nullptr;
+        int mask = -1;
+        if (n_pairs <= LSET_PAIRS) {
+            constexpr int S_MAX = LSET_CAP / 2;
+            int *own = reinterpret_cast<int *>(b.user_of<64>());                              // [max(OCAP, S_MAX)]
+            constexpr int OWN_N = OCAP > S_MAX ? OCAP : S_MAX;
+            int *in_key = own + OWN_N;                                                        // [LSET_PAIRS]
+            int *dk = in_key + LSET_PAIRS, *ord0 = dk + LSET_PAIRS, *ord1 = ord0 + LSET_PAIRS;
+            unsigned long long *in_hash = reinterpret_cast<unsigned long long *>(ord1 + LSET_PAIRS + ((OWN_N + 4 * LSET_PAIRS) & 1));
+            unsigned long long *dh = in_hash + LSET_PAIRS;
+            static_assert((size_t)(OWN_N + 4 * LSET_PAIRS + 1) * 4 + (size_t)2 * LSET_PAIRS * 8 <= (size_t)SIM_USER_BYTES, "set replay layout");
+            static_assert((size_t)LSET_PAIRS * 4 <= (size_t)OWN_N * 4, "the sorted pairs (start of the table area) end before the insert stream");
+            mask = replay(own, in_key, in_hash, dk, dh, ord0, ord1, S_MAX);
+            t_key = own;
+            set_in_lds = true;
+        } else if (HBM_REPLAY && n_pairs <= PCAP) {
+            // own: set_key [SETCAP]; in_key: tmp_int [PCAP]; ord0: tmp_int behind it [OCAP]; in_hash: set_hash [PCAP]; dh, dk, ord1: tmp_dbl
+            int *own = A.set_key;
+            int *in_key = A.tmp_int, *ord0 = A.tmp_int + PCAP;
+            unsigned long long *in_hash = A.set_hash;
+            unsigned long long *dh = reinterpret_cast<unsigned long long *>(A.tmp_dbl);
+            int *dk = reinterpret_cast<int *>(A.tmp_dbl + OCAP), *ord1 = dk + OCAP;
+            mask = replay(own, in_key, in_hash, dk, dh, ord0, ord1, SETCAP / 2);
+            t_key = own;
+            set_in_lds = true;
+        }
+        if (set_in_lds && (ranked || !ctl[1])) {                        // (ctl[1] is read behind the replay's last barrier)
+            const int n_co2_0 = sc->n_co2;
+            // read-out in slot order: a contiguous run of slots per thread, ONE block scan, then the converted sinks' coordinates fetched
+            // eight at a time (one scan and one dependent fetch per 256 slots until round 4)
+            int base = 0;
+            {
+                const int per = (mask + 1 + b.nth - 1) / b.nth;
+                const int e0 = b.tid * per < mask + 1 ? b.tid * per : mask + 1, e1 = e0 + per < mask + 1 ? e0 + per : mask + 1;
+                int cnt = 0;
+                for (int e = e0; e < e1; e++) cnt += t_key[e] >= 0 ? 1 : 0;
+                int ex2;
+                base = blk_scan(b, cnt, &ex2);
+                int dst = n_co2_0 + ex2;
+                constexpr int RB = 8;
+                for (int eb = e0; eb < e1; eb += RB) {
+                    int k[RB];
+                    V3 v[RB];
+#pragma unroll
+                    for (int u = 0; u < RB; u++) { k[u] = eb + u < e1 ? t_key[eb + u] : -1; }
+#pragma unroll
+                    for (int u = 0; u < RB; u++) v[u] = ld3(A.oxy + 3 * (k[u] >= 0 ? k[u] : 0));
+#pragma unroll
+                    for (int u = 0; u < RB; u++)
+                        if (k[u] >= 0) { if (dst < CCAP) st3(A.co2 + 3 * dst, v[u]); dst++; }
                 }
             }
             b.sync();
-            { int *t = ord; ord = ord_next; ord_next = t; }
-            n_prev = upto;
-            S = newS;
-        }
-        PSP(2);
-        for (int e = b.tid; e < S; e += b.nth) { const int pr = own[e]; own[e] = pr == EMPTY ? -1 : dk[ord[pr]]; }
-        b.sync();
-        PSP(3);
-#ifdef OCTA_SIM_DEBUG_SAT
-        dbg_n_ins = n_ins;
-#endif
-        return S - 1;
-    };
-    // the tables of the replay: in the table area for the usual <= LSET_PAIRS hits; in the sample's HBM scratch for the few iterations
-    // with more (the first iteration of a mode runs with the mode's raw radii: thousands of hits -- replayed by ONE thread until
-    // round 4, 16 of the 21 ms per sample this step took)
-    constexpr bool HBM_REPLAY = (size_t)PCAP + OCAP <= (size_t)OCAP + 2 * (size_t)NCANDCAP && (size_t)OCAP * 2 <= (size_t)OCAP * 3
-                                && PCAP <= SETCAP && OCAP <= SETCAP;
-    const int *t_key = nullptr;
-    int mask = -1;
-    if (n_pairs <= LSET_PAIRS) {
-        constexpr int S_MAX = LSET_CAP / 2;
-        int *own = reinterpret_cast<int *>(b.user_of<64>());                              // [max(OCAP, S_MAX)]
-        constexpr int OWN_N = OCAP > S_MAX ? OCAP : S_MAX;
-        int *in_key = own + OWN_N;                                                        // [LSET_PAIRS]
-        int *dk = in_key + LSET_PAIRS, *ord0 = dk + LSET_PAIRS, *ord1 = ord0 + LSET_PAIRS;
-        unsigned long long *in_hash = reinterpret_cast<unsigned long long *>(ord1 + LSET_PAIRS + ((OWN_N + 4 * LSET_PAIRS) & 1));
-        unsigned long long *dh = in_hash + LSET_PAIRS;
-        static_assert((size_t)(OWN_N + 4 * LSET_PAIRS + 1) * 4 + (size_t)2 * LSET_PAIRS * 8 <= (size_t)SIM_USER_BYTES, "set replay layout");
-        static_assert((size_t)LSET_PAIRS * 4 <= (size_t)OWN_N * 4, "the sorted pairs (start of the table area) end before the insert stream");
-        mask = replay(own, in_key, in_hash, dk, dh, ord0, ord1, S_MAX);
-        t_key = own;
-        set_in_lds = true;
-    } else if (HBM_REPLAY && n_pairs <= PCAP) {
-        // own: set_key [SETCAP]; in_key: tmp_int [PCAP]; ord0: tmp_int behind it [OCAP]; in_hash: set_hash [PCAP]; dh, dk, ord1: tmp_dbl
-        int *own = A.set_key;
-        int *in_key = A.tmp_int, *ord0 = A.tmp_int + PCAP;
-        unsigned long long *in_hash = A.set_hash;
-        unsigned long long *dh = reinterpret_cast<unsigned long long *>(A.tmp_dbl);
-        int *dk = reinterpret_cast<int *>(A.tmp_dbl + OCAP), *ord1 = dk + OCAP;
-        mask = replay(own, in_key, in_hash, dk, dh, ord0, ord1, SETCAP / 2);
-        t_key = own;
-        set_in_lds = true;
-    }
-    if (set_in_lds) {
-        const int n_co2_0 = sc->n_co2;
-        // read-out in slot order: a contiguous run of slots per thread, ONE block scan, then the converted sinks' coordinates fetched
-        // eight at a time (one scan and one dependent fetch per 256 slots until round 4)
-        int base = 0;
-        {
-            const int per = (mask + 1 + b.nth - 1) / b.nth;
-            const int e0 = b.tid * per < mask + 1 ? b.tid * per : mask + 1, e1 = e0 + per < mask + 1 ? e0 + per : mask + 1;
-            int cnt = 0;
-            for (int e = e0; e < e1; e++) cnt += t_key[e] >= 0 ? 1 : 0;
-            int ex2;
-            base = blk_scan(b, cnt, &ex2);
-            int dst = n_co2_0 + ex2;
-            constexpr int RB = 8;
-            for (int eb = e0; eb < e1; eb += RB) {
-                int k[RB];
-                V3 v[RB];
-#pragma unroll
-                for (int u = 0; u < RB; u++) { k[u] = eb + u < e1 ? t_key[eb + u] : -1; }
-#pragma unroll
-                for (int u = 0; u < RB; u++) v[u] = ld3(A.oxy + 3 * (k[u] >= 0 ? k[u] : 0));
-#pragma unroll
-                for (int u = 0; u < RB; u++)
-                    if (k[u] >= 0) { if (dst < CCAP) st3(A.co2 + 3 * dst, v[u]); dst++; }
+            PSP(4);
+            if (b.tid == 0) {
+                int n_co2 = n_co2_0 + base;
+                if (n_co2 > CCAP) { sc->err |= ERR_CO2_CAP; n_co2 = CCAP; }
+                sc->n_co2 = n_co2;
             }
-        }
-        b.sync();
-        PSP(4);
-        if (b.tid == 0) {
-            int n_co2 = n_co2_0 + base;
-            if (n_co2 > CCAP) { sc->err |= ERR_CO2_CAP; n_co2 = CCAP; }
-            sc->n_co2 = n_co2;
-        }
 #ifdef OCTA_SIM_DEBUG_SAT
-        dbg_mask = mask; dbg_base = base;
+            dbg_mask = mask; dbg_base = base;
 #endif
-    }
+        }
 #undef PSP
 #endif
-    if (!set_in_lds && b.tid == 0) {
-        PySetView S;
-        S.hash = A.set_hash; S.key = A.set_key; S.err = &sc->err; S.cap = SETCAP;
-        pyset_init(S);
-        for (int i = 0; i < n_pairs; i++) {
-            int o = (int)A.kd_idx[A.pairs[i] & IDX_MASK];
-            if (!A.ven_near[o]) pyset_add(S, o, A.hashes[o]);
-        }
-        int n_co2 = sc->n_co2;
-        for (int e = 0; e <= S.mask; e++)
-            if (S.key[e] >= 0) {
-                if (n_co2 >= CCAP) { sc->err |= ERR_CO2_CAP; break; }
-                int o = S.key[e];
-                A.co2[3 * n_co2] = A.oxy[3 * o]; A.co2[3 * n_co2 + 1] = A.oxy[3 * o + 1]; A.co2[3 * n_co2 + 2] = A.oxy[3 * o + 2];
-                n_co2++;
+        if (!set_in_lds && b.tid == 0) {
+            PySetView S;
+            S.hash = A.set_hash; S.key = A.set_key; S.err = &sc->err; S.cap = SETCAP;
+            pyset_init(S);
+            int *cw = reinterpret_cast<int *>(A.tmp_dbl);   // pass 0: distinct keys, their groups [OCAP] each; certificate tables [OCAP] x 2 + [2 OCAP]
+            static_assert((size_t)SETCAP / 2 <= (size_t)2 * OCAP, "certificate table");
+            int D = 0;
+            for (int i = 0; i < n_pairs; i++) {
+                const unsigned pr = A.pairs[i];
+                const int o = ranked ? (int)A.kd_idx[pr & IDX_MASK] : (int)(pr & IDX_MASK);
+                if (!A.ven_near[o]) {
+                    const int used = S.used;
+                    pyset_add(S, o, A.hashes[o]);
+                    if (!ranked && S.used != used) { cw[D] = o; cw[OCAP + D] = (int)(pr >> IDX_BITS); D++; }
+                }
             }
-        sc->n_co2 = n_co2;
+            if (!ranked && !pyset_order_free(cw, cw + OCAP, A.hashes, D, cw + 4 * OCAP, cw + 2 * OCAP, cw + 3 * OCAP, SETCAP / 2)) ctl[1] = 1;
+            if (ranked || !ctl[1]) {
+                int n_co2 = sc->n_co2;
+                for (int e = 0; e <= S.mask; e++)
+                    if (S.key[e] >= 0) {
+                        if (n_co2 >= CCAP) { sc->err |= ERR_CO2_CAP; break; }
+                        int o = S.key[e];
+                        A.co2[3 * n_co2] = A.oxy[3 * o]; A.co2[3 * n_co2 + 1] = A.oxy[3 * o + 1]; A.co2[3 * n_co2 + 2] = A.oxy[3 * o + 2];
+                        n_co2++;
+                    }
+                sc->n_co2 = n_co2;
+            }
+        }
+        b.sync();
+        OCTA_SUBPROF(sc, 14, t0);
+        if (!ranked && ctl[1]) continue;                              // (uniform: read behind the barrier above)
+        if (b.tid == 0) sc->kd_path[ranked ? 1 : 0]++;
+        break;
     }
-    b.sync();
-    OCTA_SUBPROF(sc, 14, t0);
 #if defined(OCTA_SIM_DEBUG_SAT) && !defined(OCTA_SIM_ITER_PROF)
     {   // digest of this call (compared between repeated runs on the host) + in-kernel recounts of every stage of step 5
         int ex, loc;
@@ -3551,7 +3651,7 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
         for (int o = b.tid; o < 2 * n_oxy; o += b.nth) mark[o] = 0;
         b.sync();
         for (int i = b.tid; i < n_pairs; i += b.nth) {
-            const int o = (int)A.kd_idx[A.pairs[i] & IDX_MASK];
+            const int o = ranked ? (int)A.kd_idx[A.pairs[i] & IDX_MASK] : (int)(A.pairs[i] & IDX_MASK);
             mark[o] = 1;
             if (!A.ven_near[o]) mark[n_oxy + o] = 1;
         }
@@ -3572,7 +3672,7 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
             c_slot_bad = blk_scan(b, loc, &ex);
             for (int o = b.tid; o < n_oxy; o += b.nth) mark[o] = 0;
             b.sync();
-            for (int i = b.tid; i < dbg_n_ins; i += b.nth) { const int k = in_key[i]; if (k >= 0 && k < n_oxy) mark[k] = 1; }
+            for (int i = b.tid; i < dbg_n_ins; i += b.nth) { const int k = (int)((unsigned)in_key[i] & IDX_MASK); if (k < n_oxy) mark[k] = 1; }
             b.sync();
             loc = 0; for (int o = b.tid; o < n_oxy; o += b.nth) loc += mark[o];
             c_in_distinct = blk_scan(b, loc, &ex);

@@ -1,5 +1,6 @@
 """Per-phase device time of the simulator: one 128-sample full-length launch with the GPU to itself; 100 MHz timers of thread 0
-(octa_sim_stats slots 8..23 = prof[0..15], 24..31 = kdprof[0..7]). usage: python tools/sim_phases.py [batch] [reps]"""
+(octa_sim_stats slots 8..23 = prof[0..15], 24..31 = kdprof[0..7]), and how many O2 -> CO2 conversions built the kd order
+(octa_sim_kd_paths). usage: python tools/sim_phases.py [batch] [reps]"""
 import os
 import sys
 import time
@@ -7,6 +8,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from octa_autosegmentation_amd import _native  # noqa: E402
 from octa_autosegmentation_amd.utils import configs  # noqa: E402
 from octa_autosegmentation_amd.vessel_graph_generation import greenhouse  # noqa: E402
 
@@ -31,6 +33,10 @@ def main():
         print(f"rep {rep}: wall {dt * 1e3:.0f} ms, kernel {res.timing['kernel_b_ms']:.0f} ms, per-sample phases sum {ph[:10].sum():.1f} ms")
         print("  " + "  ".join(f"{n} {v:.1f}" for n, v in zip(NAMES, ph)))
         print("  kd: " + "  ".join(f"{n} {v:.1f}" for n, v in zip(KD, kd)))
+        paths = np.zeros((B, 2), np.int64)       # O2 -> CO2 conversions per sample: set order certified without the kd order / kd order built
+        _native.check(sim._lib.octa_sim_kd_paths(sim._h, paths.ctypes.data), "octa_sim_kd_paths")
+        cert, built = paths.mean(axis=0)
+        print(f"  kd paths per sample: certified {cert:.1f}  built {built:.1f}  ({100 * cert / max(cert + built, 1e-9):.1f} % certified)")
         if os.environ.get("OCTA_PHASES_RAW"):     # diagnostic builds keep counts in the kd slots: raw means, and the samples' scalar statistics
             print("  kd raw: " + "  ".join(f"{v:.0f}" for v in st[:, 24:32].mean(axis=0)))
             print("  stats[0:8] (err, py_pos, murray_steps, n_bif, respec, ...): " + "  ".join(f"{v:.0f}" for v in st[:, 0:8].mean(axis=0)))
