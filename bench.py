@@ -6,13 +6,18 @@ arterial/venous rasterisation and max-combine, 1216x1216 label rasterisation + F
 Workload = BASELINE.json configs[1] (128-sample batch, rasterise to 1216x1216). `value` counts triples complete in HBM
 (edge list, image and label are device tensors: the edge list is exported by a kernel and read by the rasteriser where it is);
 `value_with_csv` is the rate of the drop-in CLI writing the reference's per-sample FILES (graph CSV + image PNG + label PNG: the
-triple as SURVEY.md 8d defines it), measured by the `files` leg of the same run.
+triple as SURVEY.md 8d defines it), measured by the `files` leg of the same --full run.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the outputs of the last step if
+--dump-outputs is given, and the JSON line (its launch, slot and CU-time figures come from the timed launches themselves). --full adds
+every leg that takes runs of its own: the rasteriser timed alone, the live rocprofv3 counter passes, the on-disk files leg, the U-Net
+training legs, the train.py and on-the-fly training loops, the voxeliser, the GAN networks and the CPU baselines (the --no-* options
+switch single legs of a --full run off).
 Multi-GPU (driver-launched with torch.distributed.run): samples are independent, every rank generates its own batch with
 its own seeds; no data-path collective (weak scaling).
 
-Every number quoted in DESIGN.md section 5 is a field of the JSON line this prints (or of profiles/).
+Every number quoted in DESIGN.md section 5 is a field of the JSON line this prints with --full (or of profiles/).
 """
 import argparse
 import json
@@ -537,17 +542,20 @@ def main():
     ap.add_argument("--no-serial-sim", dest="serial_sim", action="store_false", help="with --inflight > 1: let the persistent kernels of several launches share the GPU "
                     "(default: one persistent kernel at a time, a launch's rasterisation overlaps the NEXT launch's kernel and fills its tail; measured on one box, "
                     "group 4: in flight 1: 725, 2 serial: 744, 3 serial: 739, 2 concurrent: 644 samples/s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not run the two rocprofv3 counter passes (roofline.traffic then comes from the committed file)")
+    ap.add_argument("--full", action="store_true", help="after the headline leg, run every other measurement (rasteriser alone, counter passes, files, "
+                    "training legs, voxeliser, GAN networks, CPU baselines); a plain run measures the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not run the two rocprofv3 counter passes (roofline.traffic then comes from the "
+                    "committed file, as in a plain run)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-train", action="store_true", help="skip the secondary U-Net training measurement")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the secondary U-Net training measurement")
     ap.add_argument("--train-batch", type=int, default=4)
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the on-the-fly generation + training measurement")
-    ap.add_argument("--no-files", action="store_true", help="skip the on-disk triples leg")
-    ap.add_argument("--cpu-all-cores", action="store_true", help="also time the CPU baseline with one worker per visible core (BASELINE.md 3: 'all cores'; "
-                    "230 s on the 256-thread host of the GPU box, hence not in the default run)")
-    ap.add_argument("--no-long", dest="long", action="store_false", help="skip BASELINE configs[4] at its stated size: a 10 000-sample on-the-fly epoch (2 500 training "
-                    "steps of 4 over all ranks; about a minute on one MI355X). Round 5: part of the DEFAULT run, so that the driver's line carries end_to_end_10k_epoch")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the on-the-fly generation + training measurement")
+    ap.add_argument("--no-files", action="store_true", help="with --full: skip the on-disk triples leg")
+    ap.add_argument("--cpu-all-cores", action="store_true", help="with --full: also time the CPU baseline with one worker per visible core (BASELINE.md 3: "
+                    "'all cores'; 230 s on the 256-thread host of the GPU box, hence not in every --full run)")
+    ap.add_argument("--no-long", dest="long", action="store_false", help="with --full: skip BASELINE configs[4] at its stated size: a 10 000-sample on-the-fly "
+                    "epoch (2 500 training steps of 4 over all ranks; about a minute on one MI355X)")
     ap.add_argument("--long", dest="long", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)      # tests/test_bench_launcher.py: the launcher + one-line contract on gloo ranks, no GPU
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (rank 0) as "
@@ -556,6 +564,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run: the headline leg alone; every leg below that takes runs of its own is a --full leg
+        args.no_cpu_baseline = args.no_pmc = args.no_train = args.no_files = True
+        args.long = False
     if args.pmc_child:
         pmc_child(args.batch)
         return
@@ -768,10 +780,10 @@ def main():
                    "note": "slot-seconds held by simulator workgroups / (CUs x workgroup slots per CU x window); the remainder is the rasteriser's "
                            "kernels (they need CUs free of simulator workgroups) and dispatch gaps"}
 
-    # ---- rasteriser alone (other slots idle): HIP events on the stream the kernels go to
+    # ---- rasteriser alone (other slots idle, --full): HIP events on the stream the kernels go to
     raster = None
-    sample_ms, solo_launch_ms = sample_ms_loaded, None
-    if rank == 0:
+    sample_ms = solo_launch_ms = None                               # null in a plain run: the solo leg is a --full leg
+    if rank == 0 and args.full:
         g0 = pipeline.TripleGenerator(cfg, B)                            # ONE 128-sample batch: every sample alone on its CU
         g0.time_render = True
         best = None
@@ -822,7 +834,7 @@ def main():
     if not args.no_train and not args.no_end_to_end and world == 1:
         torch.cuda.empty_cache()
         cli_info = train_cli_leg()
-    elif world > 1:
+    elif world > 1 and args.full:
         cli_info = {"value": None, "skipped": f"world size {world}: this leg drives train.py's main() in-process on graphs it generates under /dev/shm of ONE rank; the "
                                               "data-parallel trainer is measured by unet_train / end_to_end_* (every rank) and train.py under torch.distributed.run by "
                                               "tests/test_training_cli.py (two gloo ranks)"}
@@ -919,6 +931,7 @@ def main():
             "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
+            "full": args.full,       # False: the headline leg alone; the fields of the other legs (and serial_depth's solo figures) are null
             "config": {"workload": f"configs[1]: {B}-sample vessel-graph batch (docker/vessel_graph_gen_docker_config.yml, "
                                    f"I=100+150, N=2000) + tree2img rasterise 304x304 image and 1216x1216 label",
                        "batch_per_gpu": B, "steps_per_launch": G, "launches_in_flight": n_fly, "persistent_kernels_at_a_time": sim_conc, "parallelism": f"sample-sharded x{world}, no collective",

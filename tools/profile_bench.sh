@@ -1,15 +1,16 @@
 #!/bin/bash
-# Collect the rocprofv3 evidence for bench.py on the GPU box (run through gpurun from the repo root):
-#   1. --kernel-trace --stats of the default bench command        -> gpurun_out/r03_bench_kernel_stats.csv
+# Collect the rocprofv3 evidence for bench.py on the GPU box, into OUT_DIR:
+#   1. --kernel-trace --stats of bench.py --full (without the CPU baseline, the counter passes and the long epoch)  -> TAG_bench_kernel_stats.csv
 #   2. --pmc FETCH_SIZE and --pmc WRITE_SIZE, one counter per pass, launches of the default shape (4 x 128 samples; two in flight, one persistent kernel at a time)
-#      -> gpurun_out/r03_bench_pmc_summary.csv
-# (counter passes never combined with tracing: see the task's profiling rules)
+#      -> TAG_bench_pmc_summary.csv
+# (counter passes are never combined with tracing). Every pass runs under its own time limit; the script stops at the first one that fails.
+# usage: tools/profile_bench.sh TAG OUT_DIR
 set -u
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-TAG=${1:-r06}
-OUT=gpurun_out
-mkdir -p $OUT
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_kt -- python bench.py --no-cpu-baseline --no-pmc --no-long > $OUT/${TAG}_bench_stdout.log 2>&1
+TAG=${1:?usage: tools/profile_bench.sh TAG OUT_DIR}
+OUT=$(mkdir -p "${2:?usage: tools/profile_bench.sh TAG OUT_DIR}" && cd "$2" && pwd) || exit 1
+export TMPDIR=/tmp
+cd "$(dirname "$0")/.." || exit 1
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_kt -- python bench.py --full --no-cpu-baseline --no-pmc --no-long > $OUT/${TAG}_bench_stdout.log 2>&1 || exit $?
 find $OUT/prof_kt -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_bench_kernel_stats.csv
 # the stats file averages launches of every size (512-sample launches of the headline leg, 128 / 256-sample launches of the solo, files and
 # on-the-fly legs): the per-size averages of the persistent kernel, from the raw trace, are what bench.py's roofline.avg_launch_ms (HIP
@@ -40,7 +41,7 @@ PY
 rm -rf $OUT/prof_kt   # the raw trace is large; only the summaries are kept
 grep '"metric"' $OUT/${TAG}_bench_stdout.log | tail -1 > $OUT/${TAG}_bench_line_under_rocprof.json
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 900 rocprofv3 --pmc $C --output-format csv -d $OUT/prof_$C -- python bench.py --steps 8 --warmup 4 --no-cpu-baseline --no-train --no-files --no-pmc --no-long > $OUT/${TAG}_pmc_$C.log 2>&1
+  timeout -k 10 900 rocprofv3 --pmc $C --output-format csv -d $OUT/prof_$C -- python bench.py --full --steps 8 --warmup 4 --no-cpu-baseline --no-train --no-files --no-pmc --no-long > $OUT/${TAG}_pmc_$C.log 2>&1 || exit $?
 done
 python - "$OUT" "$TAG" <<'PY'
 import csv, glob, sys, collections
