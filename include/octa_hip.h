@@ -499,6 +499,30 @@ int octa_blur_up_bwd(octa_ctx *ctx, const void *d_in, void *d_out, int dtype, in
 int octa_remove_small_objects(octa_ctx *ctx, const uint8_t *d_in, int B, int H, int W, int min_size, int connectivity,
                               uint8_t on_value, uint8_t *d_out, void *stream);
 
+/* ---- Optimally Oriented Flux (OOF) baseline (configs/config_oof.yml, reference models/oof.py) ----------
+ * Caller-owned device buffers, no context: the workspace is the caller's (size from the *_workspace_bytes functions, a function
+ * of the shape only) and must not be shared by two calls in flight. 1 <= h, w <= 4096 (any factorisation; prime factors above 5
+ * cost O(N p) per line of length N), b >= 1. */
+
+/* Bytes of workspace octa_fft2_c2c_f64 needs for b images of h x w (0 for an invalid shape). */
+size_t octa_fft2_c2c_f64_workspace_bytes(int b, int h, int w);
+
+/* Batched complex-double 2-D DFT: d_in, d_out interleaved complex double [b][h][w] (may alias). Forward: X[k][l] = sum x[m][n]
+ * exp(-2 pi i (k m / h + l n / w)); inverse (inverse != 0): the conjugate kernel times 1 / (h w), as numpy.fft.ifft2.
+ * Hand-written mixed-radix Stockham passes, twiddles from sincospi in double (csrc/oof.hip). */
+int octa_fft2_c2c_f64(const void *d_in, void *d_out, int b, int h, int w, int inverse, void *d_ws, void *stream);
+
+/* Bytes of workspace octa_oof_2d / octa_oof_2d_response need for b images of h x w (0 for an invalid shape). */
+size_t octa_oof_workspace_bytes(int b, int h, int w);
+
+/* OOF filter of the reference's fixed settings (radii 1..5, sigma 1, response_type 1, absolute eigenvalues, normalization_type 1):
+ * d_in float32 [b][h][w] in [0, 1] (multiplied by 255 in float32 as the reference does), d_out float64 [b][h][w] =
+ * (R + M) / max(R + M) per image, R the strongest response over the radii, M = max R. Deterministic; images independent. */
+int octa_oof_2d(const float *d_in, double *d_out, int b, int h, int w, void *d_ws, void *stream);
+
+/* The same without the final normalisation: d_out = R (the reference's OOF._compute_oof). */
+int octa_oof_2d_response(const float *d_in, double *d_out, int b, int h, int w, void *d_ws, void *stream);
+
 /* ---- N1-N4: space-colonisation vessel-graph simulator --------------------
  * Replaces, for B independent samples advanced in lock-step on the GPU:
  *   vessel_graph_generation/greenhouse.py:57-137 (Greenhouse.develop_forest) with

@@ -381,9 +381,27 @@ class Resized(MapTransform):
             x = data[key]
             if list(x.shape[1:]) == self.size:
                 continue
-            kw = {"align_corners": self.align_corners} if self.mode in ("bilinear", "bicubic") else {}
-            data[key] = torch.nn.functional.interpolate(x.float().unsqueeze(0), size=self.size, mode=self.mode, **kw).squeeze(0)
+            data[key] = _interpolate(x, self.size, self.mode, self.align_corners)
         return data
+
+
+def _interpolate(x, size, mode, align_corners):
+    """Channel-first [C, *spatial] -> float32 [C, *size] by torch's interpolation (MONAI Resize without anti-aliasing)."""
+    kw = {"align_corners": align_corners} if mode in ("bilinear", "bicubic") else {}
+    return torch.nn.functional.interpolate(x.float().unsqueeze(0), size=size, mode=mode, **kw).squeeze(0)
+
+
+class Resize:
+    """MONAI's Resize of a post-processing chain (configs/config_oof.yml): channel-first [C, H, W] -> float32 [C, *spatial_size],
+    `mode` area by default, no anti-aliasing; the interpolation of Resized."""
+
+    def __init__(self, spatial_size, mode="area", align_corners=None, **unused):
+        self.size, self.mode, self.align_corners = [int(v) for v in spatial_size], mode, align_corners
+
+    def __call__(self, x):
+        if list(x.shape[1:]) == self.size:
+            return x.float()
+        return _interpolate(x, self.size, self.mode, self.align_corners)
 
 
 def _spatial_dims(axes):
@@ -567,7 +585,7 @@ class CastToType:
 TRANSFORMS = {c.__name__: c for c in (
     LoadGraphAndFilterByRandomRadiusd, ToGrayScaled, SpeckleBrightnesd, AddRandomBackgroundNoised, ImageToImageTranslationd,
     LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, Flipd, RandFlipd, Rotate90d, RandRotate90d, RandRotated, AsDiscreted,
-    CastToTyped, Activations, AsDiscrete, RemoveSmallObjects, CastToType)}
+    CastToTyped, Activations, AsDiscrete, RemoveSmallObjects, Resize, CastToType)}
 
 
 def get_data_augmentations(aug_config, seed=None, dtype=torch.float32):

@@ -25,7 +25,10 @@ class LambdaModel(BaseModelABC):
                                        phase: Phase = Phase.TRAIN) -> None:
         if phase != Phase.TEST:
             self.loss_name = config.get(Phase.TRAIN, dict()).get("loss", "")
-            self.loss_function = get_loss_function_by_name(self.loss_name, config)
+            if not isinstance(self.model, torch.nn.Module) and "loss" not in config.get(Phase.TRAIN, dict()):
+                self.loss_function = None     # a parameterless model (OOF) without Train.loss: validation reports no losses
+            else:
+                self.loss_function = get_loss_function_by_name(self.loss_name, config)
         if phase == Phase.TRAIN and config[Phase.TRAIN].get("AT", False):
             raise NotImplementedError("adversarial training (Train.AT, configs *_RA / *_AA) is outside the MI355X hot path")
         super().initialize_model_and_optimizer(init_mini_batch, init_weights, config, args, scaler, phase)
@@ -43,7 +46,7 @@ class LambdaModel(BaseModelABC):
         outputs: Output = {"prediction": [post_transformations["prediction"](i) for i in decollate_batch(pred[0:1])]}
         if phase != Phase.TEST:
             outputs["label"] = [post_transformations["label"](i) for i in decollate_batch(labels[0:1])]
-            losses = {self.loss_name: self.loss_function(y_pred=pred.float(), y=labels.float())}
+            losses = {self.loss_name: self.loss_function(y_pred=pred.float(), y=labels.float())} if self.loss_function is not None else {}
         else:
             losses = None
         return outputs, losses
