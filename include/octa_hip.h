@@ -36,7 +36,8 @@ typedef struct octa_ctx octa_ctx;
 
 /* ---- library / context ------------------------------------------------- */
 
-/* ABI version of this header (bumped on incompatible change). */
+/* ABI version of this header, 2: the number changes when a declared function's signature or a struct's layout changes or a function
+ * is removed. */
 int octa_abi_version(void);
 
 /* Message of the last error on this thread ("" if none). */
@@ -167,9 +168,17 @@ int octa_instnorm_lrelu_bwd(octa_ctx *ctx, const void *d_x, const void *d_dy, co
                             int64_t hw, int dtype, float slope, void *stream);
 
 /* Channels-last variants for the MFMA convolution path: activations [B][HW][C] bfloat16, C a multiple of 8
- * (<= 512); same arithmetic and the same float32 statistics / affine gradients as the two functions above. */
+ * (<= 512); same arithmetic and the same float32 statistics / affine gradients as the two functions above.
+ * Statistics source of the forward: by default it makes a statistics pass of its own over d_x. MONAI's UnetBasicBlock is
+ * conv -> InstanceNorm(affine) -> LeakyReLU (imported at models/networks.py:6), and the convolution that wrote d_x can supply the sums:
+ *  - d_stat_partials (NULL = none), tiles: per-tile float32 partials [B][tiles][C][2] (octa_conv3x3_args.d_stat_partials, tiles =
+ *    octa_conv_stat_tiles(Ho, Wo)); they are folded instead of re-reading the tensor;
+ *  - d_stat_slots (NULL = none), nslot: the same sums in slot form, double [nslot][B][C][2], 1 <= nslot <= 1024 (octa_conv3x3_args.d_stat_slots,
+ *    octa_conv3x3_nhwc_fwd_pad, octa_conv3x3_c1_fwd): one launch, one read of d_x.
+ * At most one of the two; tiles / nslot are ignored with a NULL pointer. */
 int octa_instnorm_lrelu_nhwc_fwd(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_w, const float *d_b, float *d_mean,
-                                 float *d_rstd, int B, int C, int64_t hw, float slope, float eps, void *stream);
+                                 float *d_rstd, int B, int C, int64_t hw, float slope, float eps, const float *d_stat_partials, int tiles,
+                                 const double *d_stat_slots, int nslot, void *stream);
 int octa_instnorm_lrelu_nhwc_bwd(octa_ctx *ctx, const void *d_x, const void *d_dy, const float *d_w, const float *d_b,
                                  const float *d_mean, const float *d_rstd, void *d_dx, float *d_dw, float *d_db, int B, int C,
                                  int64_t hw, float slope, void *stream);
@@ -181,6 +190,21 @@ int octa_instnorm_nhwc_stats(octa_ctx *ctx, const void *d_x, const float *d_w, c
                              float *d_scale, float *d_shift, int B, int C, int64_t hw, float eps, void *stream);
 int octa_scale_shift_lrelu_nhwc(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_scale, const float *d_shift, int B, int C,
                                 int64_t hw, float slope, void *stream);
+
+/* InstanceNorm(affine) + LeakyReLU + 1x1 convolution to ONE channel with bias, fused: the last norm of DynUNet's decoder followed
+ * by UnetOutBlock (MONAI, imported at models/networks.py:6; 32 -> 1 channels at 1216^2). d_x [B][hw][C] bf16 (the raw output of the last
+ * 3x3 convolution), d_w / d_b the norm's affine parameters (NULL = none), d_head_w float32[C], d_head_b float32[1] or NULL ->
+ * d_logits bf16 [B][hw]; mean / rstd [B*C] are kept for backward. The normalised tensor and its gradient never reach HBM: backward
+ * rebuilds dL/dy[p][c] = dlogit[p] * head_w[c] from d_dlogits (bf16 [B][hw]) and writes d_dx (bf16), d_dw / d_db (float32[C], may be
+ * NULL), d_dhead_w (float32[C]) and d_dhead_b (float32[1] or NULL), all overwritten. C in {8, 16, 32, 64, 128, 256}.
+ * d_slots (NULL = the layer makes a statistics pass of its own; nslot then ignored): the statistics of d_x in slot form, double
+ * [nslot][B][C][2], supplied by the convolution that wrote it (octa_conv3x3_args.d_stat_slots). */
+int octa_instnorm_lrelu_head1_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_b, const float *d_head_w,
+                                       const float *d_head_b, float *d_mean, float *d_rstd, void *d_logits, int B, int C, int64_t hw,
+                                       float slope, float eps, const double *d_slots, int nslot, void *stream);
+int octa_instnorm_lrelu_head1_nhwc_bwd(octa_ctx *ctx, const void *d_x, const void *d_dlogits, const float *d_w, const float *d_b,
+                                       const float *d_head_w, const float *d_mean, const float *d_rstd, void *d_dx, float *d_dw, float *d_db,
+                                       float *d_dhead_w, float *d_dhead_b, int B, int C, int64_t hw, float slope, void *stream);
 
 /* ---- 3x3 convolution on the matrix cores, NHWC bf16 (fp32 accumulate) --------------------
  * Replaces the bias-free 3x3 convolutions of DynUNet's UnetBasicBlock / UnetUpBlock (MONAI, imported at
@@ -194,135 +218,103 @@ int octa_scale_shift_lrelu_nhwc(octa_ctx *ctx, const void *d_x, void *d_y, const
  * virtual positions, 0 elsewhere; virtual size 2H x 2W): with flipped + transposed weights that is the
  * data gradient of a stride-2 layer, with in_dilation 1 that of a stride-1 layer.
  * Ho = (H*in_dilation - 1) / stride + 1 (likewise Wo). Cin and Cout must be multiples of 32.
- */
-int octa_conv3x3_nhwc_fwd(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin,
-                          int Cout, int stride, int in_dilation, void *stream);
-
-/* Same, with a VIRTUAL channel concatenation of two inputs (channels [0, C1) from d_x [.. C1], the rest from d_x2
- * [.. Cin - C1]; d_x2 NULL = single input) and a split output (channels [0, CY1) to d_y, the rest to d_y2; d_y2
- * NULL = single output): the decoder's torch.cat((up, skip), 1) of MONAI's UnetUpBlock and its backward slicing
- * never materialise. C1 and CY1 multiples of 32.
- * tap_mask: bit 3*r+s set = tap (r, s) is evaluated; taps whose weights are structurally zero (the 2x2 transposed
- * convolution written as the adjoint of a stride-2 3x3 layer uses 4 of 9) are skipped. 0x1ff = all. */
-int octa_conv3x3_nhwc_fwd2(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2, int CY1,
-                           int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask, void *stream);
-
-/* Same, with a scattered output: result pixel (y, x) is stored at (y * out_scale + out_off_y, x * out_scale +
- * out_off_x) of a d_y image out_scale (1 or 2) times larger. With out_scale 2, one call per parity class and the
- * taps / weights of that class, a stride-2 data gradient or a 2x2 transposed convolution runs without any
- * multiplication by inserted zeros. */
-int octa_conv3x3_nhwc_fwd3(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2, int CY1,
-                           int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask, int out_scale,
-                           int out_off_y, int out_off_x, void *stream);
-
-/* Same, with NORMALISE-ON-LOAD: if d_scale1 / d_shift1 (float32 [N][C1]) are given, input 1 is the raw output of an
- * earlier convolution and is read as lrelu(x * scale + shift) -- InstanceNorm(affine) + LeakyReLU(slope) per image
- * and channel, rounded to bf16 exactly as the materialised tensor would be; likewise d_scale2 / d_shift2
- * ([N][Cin - C1]) for input 2. Padding stays zero. The normalised activations of MONAI's UnetBasicBlock then never
- * go to HBM. */
-int octa_conv3x3_nhwc_fwd4(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2, int CY1,
-                           int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask, int out_scale,
-                           int out_off_y, int out_off_x, const float *d_scale1, const float *d_shift1, const float *d_scale2,
-                           const float *d_shift2, float slope, void *stream);
-int octa_conv3x3_nhwc_wgrad3(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_dy, float *d_dw, int N, int H, int W,
-                             int Cin, int Cout, int tap_mask, const float *d_scale1, const float *d_shift1, const float *d_scale2,
-                             const float *d_shift2, float slope, void *stream);
-
-/* Same, and the statistics of the InstanceNorm that follows come for free: d_stat_partials (float32
- * [N][octa_conv_stat_tiles(Ho, Wo)][Cout][2], may be NULL) receives per output tile and channel the sum and the sum of
- * squares of the bf16-rounded results; octa_instnorm_lrelu_nhwc_fwd_p folds them instead of re-reading the tensor. */
+ *
+ * The operands travel in one struct. Zero it, set struct_size = sizeof(octa_conv3x3_args) and fill what the call uses. A zeroed POINTER
+ * field means "absent"; the four integer fields marked (*) have NO hidden default -- the plain layer is stride 1, in_dilation 1,
+ * tap_mask 0x1ff, out_scale 1, and a zero in any of them is refused, so a forgotten field is loud.
+ *  - d_x2, C1: VIRTUAL channel concatenation of two inputs (channels [0, C1) from d_x [.. C1], the rest from d_x2 [.. Cin - C1]; d_x2 NULL =
+ *    single input, C1 ignored); d_y2, CY1: split output (channels [0, CY1) to d_y, the rest to d_y2; d_y2 NULL = single output, CY1
+ *    ignored): the decoder's torch.cat((up, skip), 1) of MONAI's UnetUpBlock and its backward slicing never materialise. C1 and CY1
+ *    multiples of 32.
+ *  - tap_mask (*): bit 3*r+s set = tap (r, s) is evaluated; taps whose weights are structurally zero (the 2x2 transposed convolution
+ *    written as the adjoint of a stride-2 3x3 layer uses 4 of 9) are skipped. 0x1ff = all.
+ *  - out_scale (*), out_off_y, out_off_x: scattered output: result pixel (y, x) is stored at (y * out_scale + out_off_y, x * out_scale +
+ *    out_off_x) of a d_y image out_scale (1 or 2) times larger. With out_scale 2, one call per parity class and the taps / weights of that
+ *    class, a stride-2 data gradient or a 2x2 transposed convolution runs without any multiplication by inserted zeros.
+ *  - d_scale1 / d_shift1 (float32 [N][C1], NULL = none): NORMALISE-ON-LOAD: input 1 is the raw output of an earlier convolution and is read
+ *    as lrelu(x * scale + shift) -- InstanceNorm(affine) + LeakyReLU(slope) per image and channel, rounded to bf16 exactly as the
+ *    materialised tensor would be; likewise d_scale2 / d_shift2 ([N][Cin - C1]) for input 2. Padding stays zero. The normalised
+ *    activations of MONAI's UnetBasicBlock then never go to HBM. slope is read only with them.
+ *  - d_stat_partials (float32 [N][octa_conv_stat_tiles(Ho, Wo)][Cout][2], NULL = none): the statistics of the InstanceNorm that follows
+ *    come for free: per output tile and channel the sum and the sum of squares of the bf16-rounded results;
+ *    octa_instnorm_lrelu_nhwc_fwd folds them instead of re-reading the tensor. Plain single output only.
+ *  - d_stat_slots, nslot (NULL = none, nslot ignored): the same statistics in SLOT form: the epilogue adds, per output channel, the sum and
+ *    the sum of squares of the bf16-rounded results of every output tile to double[nslot][N][Cout][2] (ZERO on entry, 1 <= nslot <= 1024;
+ *    tile t adds to slot t % nslot, so the chain of same-address atomics stays short); octa_instnorm_lrelu_nhwc_fwd /
+ *    octa_instnorm_lrelu_head1_nhwc_fwd consume them. Plain single output; not beside d_stat_partials or normalise-on-load.
+ *  - d_residual (shape of d_y, NULL = none): ADDED to the bf16-rounded result (fp32 add, rounded again: what a separate bf16 tensor
+ *    addition would store). Used by the data gradient of a layer whose input has a second consumer -- the skip connections of the U-Net
+ *    (MONAI DynUNet, models/networks.py:6): the decoder's gradient of the skip tensor is ready first and rides along in the epilogue of the
+ *    encoder's data-gradient launch instead of a separate addition pass. Plain single output only (no scatter, split, statistics or
+ *    normalise-on-load). */
 int octa_conv_stat_tiles(int Ho, int Wo);
-int octa_conv3x3_nhwc_fwd5(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2, int CY1,
-                           int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask, int out_scale,
-                           int out_off_y, int out_off_x, const float *d_scale1, const float *d_shift1, const float *d_scale2,
-                           const float *d_shift2, float slope, float *d_stat_partials, void *stream);
-/* _fwd5 plus a residual: d_residual (NULL = none) has the shape of d_y and is ADDED to the bf16-rounded result (fp32 add, rounded
- * again: what a separate bf16 tensor addition would store). Used by the data gradient of a layer whose input has a second
- * consumer -- the skip connections of the U-Net (MONAI DynUNet, models/networks.py:6): the decoder's gradient of the skip tensor is
- * ready first and rides along in the epilogue of the encoder's data-gradient launch instead of a separate addition pass. Plain single
- * output only (no scatter, split, statistics or normalise-on-load). */
-int octa_conv3x3_nhwc_fwd6(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2, int CY1,
-                           int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask, int out_scale,
-                           int out_off_y, int out_off_x, const float *d_scale1, const float *d_shift1, const float *d_scale2,
-                           const float *d_shift2, float slope, float *d_stat_partials, const void *d_residual, void *stream);
-/* The two layers of the U-Net whose output is twice the size of their input, with the four output parities fused (round 5): the data
+typedef struct octa_conv3x3_args {
+    uint32_t struct_size;                    /* sizeof(octa_conv3x3_args): checked first, the error text names both sizes */
+    int N, H, W, Cin, Cout;
+    int stride, in_dilation, tap_mask;       /* (*) */
+    int out_scale, out_off_y, out_off_x;     /* (*) out_scale */
+    int C1, CY1, nslot;
+    float slope;
+    const void *d_x, *d_x2, *d_w;
+    void *d_y, *d_y2;
+    const float *d_scale1, *d_shift1, *d_scale2, *d_shift2;
+    float *d_stat_partials;
+    double *d_stat_slots;
+    const void *d_residual;
+} octa_conv3x3_args;
+int octa_conv3x3_nhwc_fwd(octa_ctx *ctx, const octa_conv3x3_args *args, void *stream);
+
+/* The two layers of the U-Net whose output is twice the size of their input, with the four output parities fused: the data
  * gradient of a stride-2 3x3 convolution (MONAI UnetBasicBlock with stride 2) and the 2x2 stride-2 transposed convolution (UnetUpBlock.transp_conv;
  * both imported at models/networks.py:6). d_x [N][H][W][Cin] bf16 is the SMALL image, d_w [9][Cout][Cin] bf16 the pack the zero-insertion form
- * reads (octa_conv3x3_nhwc_fwd2 with in_dilation = 2 computes the same sums, three quarters of them against inserted zeros), d_y
+ * reads (octa_conv3x3_nhwc_fwd with in_dilation = 2 computes the same sums, three quarters of them against inserted zeros), d_y
  * [N][2H][2W][Cout] bf16. tap_mask: 0x1ff (data gradient of a stride-2 layer) or 0b000011011 (the transposed convolution: one tap per parity).
- * d_residual (shape of d_y, NULL = none) is added as octa_conv3x3_nhwc_fwd6 adds it. Cin, Cout multiples of 32. */
+ * d_residual (shape of d_y, NULL = none) is added as octa_conv3x3_nhwc_fwd adds it. Cin, Cout multiples of 32. */
 int octa_conv3x3_s2t_nhwc(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int tap_mask,
                           const void *d_residual, void *stream);
-/* InstanceNorm(affine) + LeakyReLU + 1x1 convolution to ONE channel with bias, fused: the last norm of DynUNet's decoder followed
- * by UnetOutBlock (MONAI, imported at models/networks.py:6; 32 -> 1 channels at 1216^2). d_x [B][hw][C] bf16 (the raw output of the last
- * 3x3 convolution), d_w / d_b the norm's affine parameters (NULL = none), d_head_w float32[C], d_head_b float32[1] or NULL ->
- * d_logits bf16 [B][hw]; mean / rstd [B*C] are kept for backward. The normalised tensor and its gradient never reach HBM: backward
- * rebuilds dL/dy[p][c] = dlogit[p] * head_w[c] from d_dlogits (bf16 [B][hw]) and writes d_dx (bf16), d_dw / d_db (float32[C], may be
- * NULL), d_dhead_w (float32[C]) and d_dhead_b (float32[1] or NULL), all overwritten. C in {8, 16, 32, 64, 128, 256}. */
-int octa_instnorm_lrelu_head1_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_b, const float *d_head_w,
-                                       const float *d_head_b, float *d_mean, float *d_rstd, void *d_logits, int B, int C, int64_t hw,
-                                       float slope, float eps, void *stream);
-/* octa_instnorm_lrelu_head1_nhwc_fwd with the statistics of d_x supplied in slot form (double [nslot][B][C][2]) by the convolution that wrote it
- * (octa_conv3x3_nhwc_fwd7): the layer then makes no statistics pass of its own. */
-int octa_instnorm_lrelu_head1_nhwc_fwd_s(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_b, const float *d_head_w,
-                                         const float *d_head_b, float *d_mean, float *d_rstd, void *d_logits, int B, int C, int64_t hw,
-                                         float slope, float eps, const double *d_slots, int nslot, void *stream);
-int octa_instnorm_lrelu_head1_nhwc_bwd(octa_ctx *ctx, const void *d_x, const void *d_dlogits, const float *d_w, const float *d_b,
-                                       const float *d_head_w, const float *d_mean, const float *d_rstd, void *d_dx, float *d_dw, float *d_db,
-                                       float *d_dhead_w, float *d_dhead_b, int B, int C, int64_t hw, float slope, void *stream);
-int octa_instnorm_lrelu_nhwc_fwd_p(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_w, const float *d_b, float *d_mean,
-                                   float *d_rstd, int B, int C, int64_t hw, float slope, float eps, const float *d_partials, int tiles,
-                                   void *stream);
-/* The same statistics in SLOT form (round 5): MONAI's UnetBasicBlock is conv -> InstanceNorm(affine) -> LeakyReLU (imported at
- * models/networks.py:6); octa_conv3x3_nhwc_fwd7 is octa_conv3x3_nhwc_fwd2 (one or two virtually concatenated inputs, stride 1 or 2,
- * plain single output d_y [N][Ho][Wo][Cout]) whose epilogue also adds, per output channel, the sum and the sum of squares of the
- * bf16-rounded results of every output tile to d_stat_slots = double[nslot][N][Cout][2] (ZERO on entry, 1 <= nslot <= 1024; tile t adds
- * to slot t % nslot, so the chain of same-address atomics stays short). octa_instnorm_lrelu_nhwc_fwd_s is
- * octa_instnorm_lrelu_nhwc_fwd with those slots instead of its own statistics pass over d_x: one launch, one read of d_x. */
-int octa_conv3x3_nhwc_fwd7(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, int N, int H, int W,
-                           int Cin, int Cout, int stride, double *d_stat_slots, int nslot, void *stream);
-int octa_instnorm_lrelu_nhwc_fwd_s(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_w, const float *d_b, float *d_mean,
-                                   float *d_rstd, int B, int C, int64_t hw, float slope, float eps, const double *d_stat_slots, int nslot,
-                                   void *stream);
 
-/* 3 x 3 convolution, stride 1, with an explicit padding (round 3): pad = 0 (valid), 1 (same), 2 (full: the data gradient of a valid
+/* 3 x 3 convolution, stride 1, with an explicit padding: pad = 0 (valid), 1 (same), 2 (full: the data gradient of a valid
  * convolution), zeros outside the image; reflect = 1 (pad = 1 only) fuses nn.ReflectionPad2d(1) into the halo fetch -- the ResNet
  * blocks of the reference's generator (models/networks.py:151-176: ReflectionPad2d(1) + Conv2d(3, padding 0)) without a padded or a
  * cropped copy. d_x [N][H][W][Cin], d_w packed [9][Cout][Cin], d_y [N][H + 2 pad - 2][W + 2 pad - 2][Cout], all bf16; Cin, Cout
- * multiples of 32. octa_conv3x3_nhwc_wgrad_pad is its weight gradient (d_dw fp32 [9][Cout][Cin], overwritten). */
+ * multiples of 32. d_stat_slots, nslot (NULL, 0 = none): the InstanceNorm statistics of the result accumulated by the kernel's epilogue in
+ * slot form (double [nslot][N][Cout][2], zeroed by the caller, consumed by octa_instnorm_lrelu_nhwc_fwd; as octa_conv3x3_args.d_stat_slots):
+ * the generator's residual blocks are reflect-padded convolution -> InstanceNorm (models/networks.py:151-176), 18 per pass. */
 int octa_conv3x3_nhwc_fwd_pad(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int pad,
-                              int reflect, void *stream);
+                              int reflect, double *d_stat_slots, int nslot, void *stream);
+
+/* Weight gradient of octa_conv3x3_nhwc_fwd: sum over pixels of d_dy[N][Ho][Wo][Cout] (bf16) x d_x[N][H][W][Cin] (bf16) shifted by the tap
+ * (octa_conv2d_wgrad), fp32 accumulation; where the partial sums of the persistent workgroups meet in fp32 atomics, the
+ * last bits depend on the arrival order. Struct rules as octa_conv3x3_args: zero it, set struct_size, fill; stride and
+ * tap_mask have no hidden default (the plain layer is stride 1, tap_mask 0x1ff; zero is refused).
+ *  - d_x2, C1: the virtual input concatenation of the forward (d_x2 NULL = single input, C1 ignored).
+ *  - stride: 1, or 2 = d_x is the [N][H][W][Cin] input of a stride-2 layer (H, W even), d_dy its [N][H/2][W/2][Cout] output gradient.
+ *  - tap_mask: as in the forward (the 2x2 transposed convolution, written as the adjoint of a stride-2 layer, asks for 4 of the 9 taps);
+ *    taps outside it are left / add zero.
+ *  - d_scale1 .. d_shift2, slope (NULL = none): the forward's normalise-on-load vectors, applied to d_x / d_x2 while loading. Stride 1, or
+ *    a plain stride-2 tensor; OCTA_WGRAD_TAP_MAJOR only.
+ *  - out_mode: OCTA_WGRAD_TAP_MAJOR: d_dw is float32 [9][Cout][Cin], overwritten. OCTA_WGRAD_PARAM_ADD: the gradient is ADDED to d_dw, a
+ *    buffer in the parameter's own layout, float32 [Cout][Cin][3][3] (models/networks.py / MONAI state-dict layout;
+ *    base_model_abc.py:152-167's `loss.backward()` accumulates into exactly this tensor): the training step passes `weight.grad`, a view of
+ *    its flat gradient arena -- no [9][Cout][Cin] temporary, fill, layout copy or accumulation launch per layer. OCTA_WGRAD_PARAM_SET:
+ *    the same layout, overwritten. */
+enum { OCTA_WGRAD_TAP_MAJOR = 0, OCTA_WGRAD_PARAM_ADD = 1, OCTA_WGRAD_PARAM_SET = 2 };
+typedef struct octa_conv3x3_wgrad_args {
+    uint32_t struct_size;                    /* sizeof(octa_conv3x3_wgrad_args): checked first, the error text names both sizes */
+    int N, H, W, Cin, Cout;
+    int stride, tap_mask;                    /* no hidden default */
+    int C1, out_mode;
+    float slope;
+    const void *d_x, *d_x2, *d_dy;
+    float *d_dw;
+    const float *d_scale1, *d_shift1, *d_scale2, *d_shift2;
+} octa_conv3x3_wgrad_args;
+int octa_conv3x3_nhwc_wgrad(octa_ctx *ctx, const octa_conv3x3_wgrad_args *args, void *stream);
+
+/* Weight gradient of octa_conv3x3_nhwc_fwd_pad (same pad / reflect; d_dy [N][H + 2 pad - 2][W + 2 pad - 2][Cout]); out_mode and d_dw as in
+ * octa_conv3x3_wgrad_args. */
 int octa_conv3x3_nhwc_wgrad_pad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cin, int Cout, int pad,
-                                int reflect, void *stream);
-/* octa_conv3x3_nhwc_fwd_pad with the InstanceNorm statistics of the result accumulated by the kernel's epilogue in slot form (d_stat_slots: double
- * [nslot][N][Cout][2], zeroed by the caller, consumed by octa_instnorm_lrelu_nhwc_fwd_s; as octa_conv3x3_nhwc_fwd7): the generator's residual
- * blocks are reflect-padded convolution -> InstanceNorm (models/networks.py:151-176), 18 per pass. NULL slots = octa_conv3x3_nhwc_fwd_pad. */
-int octa_conv3x3_nhwc_fwd_pad_s(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int pad,
-                                int reflect, double *d_stat_slots, int nslot, void *stream);
-
-/* Weight gradient with a stride: stride 2 = d_x is the [N][H][W][Cin] input of a stride-2 layer (H, W even), d_dy its
- * [N][H/2][W/2][Cout] output gradient; tap_mask as above (the 2x2 transposed convolution, written as the adjoint of a
- * stride-2 layer, asks for 4 of the 9 taps). */
-int octa_conv3x3_nhwc_wgrad4(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_dy, float *d_dw, int N, int H, int W,
-                             int Cin, int Cout, int stride, int tap_mask, const float *d_scale1, const float *d_shift1,
-                             const float *d_scale2, const float *d_shift2, float slope, void *stream);
-
-/* The weight gradient ADDED to a gradient buffer in the parameter's own layout, float32 [Cout][Cin][3][3] (models/networks.py / MONAI
- * state-dict layout; base_model_abc.py:152-167's `loss.backward()` accumulates into exactly this tensor): the training step passes
- * `weight.grad`, a view of its flat gradient arena -- no [9][Cout][Cin] temporary, fill, layout copy or accumulation launch per layer.
- * Operands as octa_conv3x3_nhwc_wgrad4 without the normalise-on-load vectors (stride 1, or 2 with even H, W); taps outside tap_mask add
- * zero. octa_conv3x3_nhwc_wgrad_pad_acc: the same for octa_conv3x3_nhwc_wgrad_pad. */
-int octa_conv3x3_nhwc_wgrad_acc(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_dy, float *d_grad, int N, int H, int W,
-                                int Cin, int Cout, int stride, int tap_mask, int accumulate, void *stream);
-int octa_conv3x3_nhwc_wgrad_pad_acc(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_grad, int N, int H, int W, int Cin, int Cout,
-                                    int pad, int reflect, int accumulate, void *stream);
-
-/* Weight gradient of the stride-1 layer above: d_dw [9][Cout][Cin] float32 (overwritten) =
- * sum over pixels of d_dy[N][H][W][Cout] (bf16) x d_x[N][H][W][Cin] (bf16) shifted by the tap (SURVEY.md 8b:
- * octa_conv2d_wgrad). fp32 accumulation; partial sums of the persistent workgroups meet in fp32 atomics, so the
- * last bits depend on the arrival order. */
-int octa_conv3x3_nhwc_wgrad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cin,
-                            int Cout, void *stream);
+                                int reflect, int out_mode, void *stream);
 
 /* Single-precision convolution on the matrix cores (v_mfma_f32_32x32x2_f32: fp32 operands, fp32 accumulation), NCHW: the
  * convolutions of the reference's paths that run WITHOUT mixed precision -- test.py:79 / validate.py call model.inference outside
@@ -372,13 +364,11 @@ int octa_conv4x4_nhwc_wgrad(octa_ctx *ctx, const void *d_x, const void *d_dy, fl
 
 /* 1x1 convolution head with ONE output channel and bias (DynUNet's UnetOutBlock, 32 -> 1; networks.py:6 / MONAI):
  * y[p] = bias + sum_c x[p][c] w[c] over NHWC bf16 pixels (y bf16 [npix]); backward: dx[p][c] = dy[p] w[c] (bf16),
- * dw[c] = sum_p x[p][c] dy[p], db = sum_p dy[p] (float32, overwritten). HBM-bound streaming kernels. */
-int octa_head1_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, float bias, int64_t npix, int C, void *d_y, void *stream);
+ * dw[c] = sum_p x[p][c] dy[p], db = sum_p dy[p] (float32, overwritten). HBM-bound streaming kernels. The bias is read from device
+ * memory (d_bias float32[1], NULL = none): the training step never reads the parameter back to the host. */
+int octa_head1_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_bias, int64_t npix, int C, void *d_y, void *stream);
 int octa_head1_nhwc_bwd(octa_ctx *ctx, const void *d_x, const void *d_dy, const float *d_w, int64_t npix, int C, void *d_dx,
                         float *d_dw, float *d_db, void *stream);
-/* The same forward with the bias read from device memory (d_bias float32[1] or NULL): the training step never reads the
- * parameter back to the host. */
-int octa_head1_nhwc_fwd_b(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_bias, int64_t npix, int C, void *d_y, void *stream);
 
 /* Every KxK convolution weight of a network into both layouts the MFMA kernels read, in ONE launch per optimiser step
  * (the master copies stay float32 torch parameters in the reference's state-dict layout, models/networks.py /
@@ -389,11 +379,6 @@ int octa_head1_nhwc_fwd_b(octa_ctx *ctx, const void *d_x, const float *d_w, cons
  * off_dg, both in the slice-major storage order described at octa_conv3x3_nhwc_fwd (a layer whose A is no multiple of 16 keeps its
  * data-gradient pack tap-major: no MFMA kernel reads it); columns B..BP-1 (channel padding to the kernels' multiple of 32) are zero. */
 int octa_pack_conv_weights(octa_ctx *ctx, const int64_t *d_table, int L, void *d_dst, void *stream);
-
-int octa_conv3x3_nhwc_wgrad2(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_dy, float *d_dw, int N, int H, int W,
-                             int Cin, int Cout, int tap_mask, void *stream);   /* wgrad with the virtual input concatenation and
-                                                                                  the tap mask of _fwd2 (unmasked taps of d_dw
-                                                                                  are left zero) */
 
 /* ---- GPU data-augmentation chain between rasteriser and network --------------------
  * Replaces the MONAI CPU transforms of configs/config_ves_seg-S.yml:42-102 (registry data/data_transforms.py:587-611)
@@ -426,14 +411,13 @@ int octa_flip_rot90_rotate(octa_ctx *ctx, const float *d_in, float *d_out, int B
 
 /* First layer of the U-Net (UnetBasicBlock.conv1 of the input block: ONE input channel -> Cout in {8, 16, 32, 64}, 3x3,
  * padding 1, stride 1): d_x [N][H][W] bf16, d_w float32 [Cout][9] (tap = 3r + s), d_y [N][H][W][Cout] bf16; the weight
- * gradient d_dw float32 [Cout][9] (overwritten). Streaming kernels: 9 multiply-adds per output are not matrix-core work. */
-int octa_conv3x3_c1_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, void *d_y, int N, int H, int W, int Cout, void *stream);
+ * gradient d_dw float32 [Cout][9] (overwritten). Streaming kernels: 9 multiply-adds per output are not matrix-core work.
+ * d_stat, nslot (NULL, 0 = none): the InstanceNorm statistics of the result accumulated in the forward kernel's epilogue, double
+ * [nslot][N][Cout][2] (pre-zeroed; sum and sum of squares of the bf16-rounded values per image and channel, spread over the slots -- the
+ * contract of octa_conv3x3_args.d_stat_slots, consumed by octa_instnorm_lrelu_nhwc_fwd). W <= 3840. */
+int octa_conv3x3_c1_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, void *d_y, int N, int H, int W, int Cout, double *d_stat, int nslot,
+                        void *stream);
 int octa_conv3x3_c1_wgrad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cout, void *stream);
-/* octa_conv3x3_c1_fwd with the InstanceNorm statistics of its result accumulated in the kernel's epilogue: d_stat double [nslot][N][Cout][2]
- * (pre-zeroed; sum and sum of squares of the bf16-rounded values per image and channel, spread over the slots -- the contract of
- * octa_conv3x3_nhwc_fwd7, consumed by octa_instnorm_lrelu_nhwc_fwd_s); d_stat NULL = octa_conv3x3_c1_fwd. W <= 3840. */
-int octa_conv3x3_c1_fwd2(octa_ctx *ctx, const void *d_x, const float *d_w, void *d_y, int N, int H, int W, int Cout, double *d_stat, int nslot,
-                         void *stream);
 
 /* ---- DiceBCELoss in one pass each way --------------------
  * utils/losses.py:111-121: (DiceLoss(sigmoid=True) + BCEWithLogitsLoss) / 2 over logits [B][n] (dtype 0 = float32,
@@ -464,7 +448,7 @@ int octa_thinconv_expand(octa_ctx *ctx, const void *d_s, const void *d_w, const 
 int octa_thinconv_squeeze(octa_ctx *ctx, const void *d_a, const void *d_w, const void *d_bias, void *d_out, int N, int Ha, int Wa, int C, int K,
                           int pad, int flip, void *stream);
 /* (octa_thinconv_squeeze also takes K = 3 with 8, 16, 32 or 64 channels: the data gradient of the one-channel 3 x 3 first layer whose forward and
- * weight gradient are octa_conv3x3_c1_fwd2 / octa_conv3x3_c1_wgrad -- dx = squeeze(dy, w, K = 3, pad = 1, flip = 1) -- for a segmentor whose
+ * weight gradient are octa_conv3x3_c1_fwd / octa_conv3x3_c1_wgrad -- dx = squeeze(dy, w, K = 3, pad = 1, flip = 1) -- for a segmentor whose
  * input image is another network's output, models/gan_seg_model.py:147-149.) */
 long long octa_thinconv_wgrad_scratch_floats(int N, int Ha, int C, int K);
 /* LeakyReLU' on a gradient by the sign of the layer's bf16 OUTPUT: out[i] = y[i] > 0 ? dy[i] : bf16(dy[i] * slope), n elements, 16-byte aligned

@@ -16,6 +16,19 @@ _lock = threading.Lock()
 
 c_void_p, c_int, c_double, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
 
+
+def _struct(name, ints, ptrs):
+    """ctypes mirror of an argument struct of include/octa_hip.h: uint32 struct_size, the int fields, float slope, the pointer fields."""
+    fields = [("struct_size", ctypes.c_uint32)] + [(k, c_int) for k in ints.split()] + [("slope", ctypes.c_float)] + [(k, c_void_p) for k in ptrs.split()]
+    return type(name, (ctypes.Structure,), {"_fields_": fields})
+
+
+# zero = absent, except stride / in_dilation / tap_mask / out_scale: no hidden default, the plain layer is 1 / 1 / 0x1ff / 1
+Conv3x3Args = _struct("Conv3x3Args", "N H W Cin Cout stride in_dilation tap_mask out_scale out_off_y out_off_x C1 CY1 nslot",
+                      "d_x d_x2 d_w d_y d_y2 d_scale1 d_shift1 d_scale2 d_shift2 d_stat_partials d_stat_slots d_residual")
+Conv3x3WgradArgs = _struct("Conv3x3WgradArgs", "N H W Cin Cout stride tap_mask C1 out_mode", "d_x d_x2 d_dy d_dw d_scale1 d_shift1 d_scale2 d_shift2")
+WGRAD_TAP_MAJOR, WGRAD_PARAM_ADD, WGRAD_PARAM_SET = 0, 1, 2     # out_mode
+
 # symbol -> (restype, argtypes); must list every function include/octa_hip.h declares
 SIGNATURES = {
     "octa_abi_version": (c_int, []),
@@ -79,14 +92,9 @@ SIGNATURES = {
     "octa_conv2d_f32_wgrad_workspace": (c_int, [c_int] * 10 + [ctypes.POINTER(c_size_t)]),
     "octa_conv2d_f32_wgrad_nchw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t] + [c_int] * 10 + [c_void_p]),
     "octa_sim_fields": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, ctypes.c_int64, c_void_p]),
-    "octa_instnorm_lrelu_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p]),
     "octa_instnorm_lrelu_nhwc_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, c_void_p]),
-    "octa_head1_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_int64, c_int, c_void_p, c_void_p]),
-    "octa_head1_nhwc_fwd_b": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p]),
     "octa_pack_conv_weights": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "octa_head1_nhwc_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "octa_conv3x3_nhwc_fwd2": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "octa_conv3x3_nhwc_fwd3": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "octa_instnorm_nhwc_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, c_void_p]),
     "octa_scale_shift_lrelu_nhwc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, c_void_p]),
     "octa_resize_bilinear": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -104,32 +112,20 @@ SIGNATURES = {
     "octa_dice_bce_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p]),
     "octa_dice_bce_finish": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_int64, c_double, c_double, c_void_p, c_void_p]),
     "octa_dice_bce_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p]),
-    "octa_conv3x3_c1_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "octa_conv3x3_nhwc_wgrad_acc": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "octa_conv3x3_nhwc_wgrad_pad_acc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "octa_sim_launch_count": (ctypes.c_longlong, []),
     "octa_order_wait_launch": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p]),
-    "octa_conv3x3_c1_fwd2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "octa_conv3x3_c1_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "octa_conv_stat_tiles": (c_int, [c_int, c_int]),
-    "octa_conv3x3_nhwc_fwd5": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p]),
-    "octa_conv3x3_nhwc_fwd6": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
-    "octa_instnorm_lrelu_head1_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p]),
-    "octa_instnorm_lrelu_head1_nhwc_fwd_s": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_int, c_void_p]),
     "octa_instnorm_lrelu_head1_nhwc_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, c_void_p]),
-    "octa_instnorm_lrelu_nhwc_fwd_p": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_int, c_void_p]),
     "octa_conv3x3_s2t_nhwc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "octa_conv3x3_nhwc_fwd7": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "octa_instnorm_lrelu_nhwc_fwd_s": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_int, c_void_p]),
-    "octa_conv3x3_nhwc_fwd4": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
-    "octa_conv3x3_nhwc_wgrad3": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
-    "octa_conv3x3_nhwc_wgrad4": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
-    "octa_conv3x3_nhwc_fwd_pad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "octa_conv3x3_nhwc_fwd_pad_s": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "octa_conv3x3_nhwc_wgrad_pad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "octa_conv3x3_nhwc_wgrad2": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "octa_conv3x3_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "octa_conv3x3_nhwc_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "octa_conv3x3_nhwc_fwd": (c_int, [c_void_p, ctypes.POINTER(Conv3x3Args), c_void_p]),
+    "octa_conv3x3_nhwc_wgrad": (c_int, [c_void_p, ctypes.POINTER(Conv3x3WgradArgs), c_void_p]),
+    "octa_conv3x3_nhwc_fwd_pad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "octa_conv3x3_nhwc_wgrad_pad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "octa_instnorm_lrelu_nhwc_fwd": (c_int, [c_void_p] * 7 + [c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "octa_instnorm_lrelu_head1_nhwc_fwd": (c_int, [c_void_p] * 9 + [c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_int, c_void_p]),
+    "octa_head1_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p]),
+    "octa_conv3x3_c1_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "octa_fft2_c2c_f64_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "octa_fft2_c2c_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "octa_oof_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

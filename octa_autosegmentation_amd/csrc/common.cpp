@@ -11,7 +11,7 @@ void set_error(const char *fmt, ...) {
 }
 }  // namespace octa
 
-extern "C" int octa_abi_version(void) { return 1; }
+extern "C" int octa_abi_version(void) { return 2; }
 
 extern "C" const char *octa_last_error(void) { return octa::g_err; }
 

@@ -786,7 +786,7 @@ conv3x3_s2t_kernel(const unsigned short *__restrict__ X, const unsigned short *_
             if (oy < Ho && ox < Wo) {
                 const size_t off = (((size_t)n * Ho + oy) * Wo + ox) * Cout + co0 + q * 8;
                 uint4 v = *reinterpret_cast<const uint4 *>(s_out + p * OP + q * 16);
-                if (R) {        // the other gradient of a skip tensor, added as octa_conv3x3_nhwc_fwd6 adds it (fp32 add of the rounded values, rounded again)
+                if (R) {        // the other gradient of a skip tensor, added as octa_conv3x3_nhwc_fwd adds it (fp32 add of the rounded values, rounded again)
                     const uint4 r = *reinterpret_cast<const uint4 *>(R + off);
                     unsigned av[4] = {v.x, v.y, v.z, v.w};
                     const unsigned bv[4] = {r.x, r.y, r.z, r.w};
@@ -822,12 +822,20 @@ int launch_conv_s2t(const unsigned short *X, const unsigned short *Wt, unsigned 
 
 extern "C" int octa_conv_stat_tiles(int Ho, int Wo) { return ((Wo + TW - 1) / TW) * ((Ho + TH - 1) / TH); }
 
-namespace {
-int conv3x3_fwd_impl(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2,
-                     int CY1, int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask,
-                     int out_scale, int out_off_y, int out_off_x, const float *d_scale1, const float *d_shift1,
-                     const float *d_scale2, const float *d_shift2, float slope, float *d_stat_partials,
-                     const void *d_residual, double *d_stat_slots, int nslot, void *stream_) {
+// The one 3x3 forward entry point (include/octa_hip.h: octa_conv3x3_args): one or two virtually concatenated inputs, split output, tap mask,
+// parity scatter, normalise-on-load, per-tile or slot statistics of the result, residual epilogue.
+extern "C" int octa_conv3x3_nhwc_fwd(octa_ctx *ctx, const octa_conv3x3_args *a, void *stream_) {
+    if (!a) { octa::set_error("octa_conv3x3_nhwc_fwd: null pointer"); return -2; }
+    if (a->struct_size != sizeof(octa_conv3x3_args)) { octa::set_error("octa_conv3x3_nhwc_fwd: struct_size %u, this library's octa_conv3x3_args has %zu bytes", a->struct_size, sizeof(octa_conv3x3_args)); return -2; }
+    const void *d_x = a->d_x, *d_x2 = a->d_x2, *d_w = a->d_w, *d_residual = a->d_residual;
+    void *d_y = a->d_y, *d_y2 = a->d_y2;
+    int C1 = a->C1, CY1 = a->CY1, tap_mask = a->tap_mask, nslot = a->nslot;
+    const int N = a->N, H = a->H, W = a->W, Cin = a->Cin, Cout = a->Cout, stride = a->stride, in_dilation = a->in_dilation;
+    const int out_scale = a->out_scale, out_off_y = a->out_off_y, out_off_x = a->out_off_x;
+    const float *d_scale1 = a->d_scale1, *d_shift1 = a->d_shift1, *d_scale2 = a->d_scale2, *d_shift2 = a->d_shift2;
+    const float slope = a->slope;
+    float *d_stat_partials = a->d_stat_partials;
+    double *d_stat_slots = a->d_stat_slots;
     if (!ctx || !d_x || !d_w || !d_y) { octa::set_error("octa_conv3x3_nhwc_fwd: null pointer"); return -2; }
     if (N <= 0 || H <= 0 || W <= 0) { octa::set_error("octa_conv3x3_nhwc_fwd: bad shape"); return -2; }
     if (Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) { octa::set_error("octa_conv3x3_nhwc_fwd: Cin and Cout must be multiples of 32 (got %d, %d)", Cin, Cout); return -2; }
@@ -844,13 +852,13 @@ int conv3x3_fwd_impl(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, c
         octa::set_error("octa_conv3x3_nhwc_fwd: output scatter must be scale 1 or 2 with offsets below the scale");
         return -2;
     }
-    if (d_stat_slots && (nslot <= 0 || nslot > 1024 || d_stat_partials || d_scale1 || d_scale2)) { octa::set_error("octa_conv3x3_nhwc_fwd: statistics slots need 1..1024 slots, no per-tile partials beside them and the DMA-staged kernel"); return -2; }
+    if (d_stat_slots && (nslot <= 0 || nslot > 1024 || d_stat_partials || d_scale1 || d_scale2)) { octa::set_error("octa_conv3x3_nhwc_fwd: statistics slots need 1..1024 slots and neither per-tile partials nor normalise-on-load operands beside them"); return -2; }
     if (!d_stat_slots) nslot = 0;
     if (d_stat_slots) d_stat_partials = reinterpret_cast<float *>(d_stat_slots);      // one kernel argument: read as double slots when nslot > 0
     if (d_stat_partials && (out_scale != 1 || d_y2)) { octa::set_error("octa_conv3x3_nhwc_fwd: statistics need a plain single output"); return -2; }
     const unsigned short *Rz = static_cast<const unsigned short *>(d_residual);
     if (Rz && (out_scale != 1 || d_y2 || d_scale1 || d_scale2 || d_stat_partials || d_residual == d_y)) {
-        octa::set_error("octa_conv3x3_nhwc_fwd: the residual needs a plain single output on the DMA-staged kernel");
+        octa::set_error("octa_conv3x3_nhwc_fwd: the residual needs a plain single output without normalise-on-load operands or statistics");
         return -2;
     }
     if ((d_scale1 == nullptr) != (d_shift1 == nullptr) || (d_scale2 == nullptr) != (d_shift2 == nullptr)) { octa::set_error("octa_conv3x3_nhwc_fwd: scale and shift come in pairs"); return -2; }
@@ -863,9 +871,9 @@ int conv3x3_fwd_impl(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, c
     const unsigned short *Wt = static_cast<const unsigned short *>(d_w);
     unsigned short *Y = static_cast<unsigned short *>(d_y), *Y2 = static_cast<unsigned short *>(d_y2);
     const bool wide = (Cout % 64 == 0) && (CY1 % 64 == 0);   // a 64-channel block must not straddle the output split
-    // plain stride-1 layers: the DMA-staged kernel (OCTA_CONV_GLDS=0 selects the register-staged one, =16 (default) / =32 the slice depth)
-    constexpr int glds_mode = 16;        // DMA-staged kernels with 16-channel slices (rounds 3-5 A/B'd 0 / 16 / 32 through OCTA_CONV_GLDS; 16 ships)
-    if (glds_mode && !d_scale1 && !d_scale2) {
+    // without normalise-on-load operands: the DMA-staged kernels, 16-channel slices (only they have the residual and the slot epilogue,
+    // both refused above beside scale / shift); with them: the register-staged kernels below
+    if (!d_scale1 && !d_scale2) {
         const unsigned short *z = zero_page(ctx);
         if (!z) return -1;
         if (stride == 2)
@@ -873,82 +881,21 @@ int conv3x3_fwd_impl(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, c
                         : launch_conv_glds<32, 16, 2>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, 1, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot);
         // 16-row tiles (a wave owns four tile rows: 6 operand reads per 8 MFMAs instead of 4 per 4, 72 MFMAs per barrier) from
         // 200 output rows up: 8-14 % faster on the 304^2 / 608^2 layers (256->128 at 304^2: 1.0 PFLOP/s), no gain at 152^2
-        // (half as many workgroups: tail effects) and on the HBM-bound 1216^2 layers. OCTA_CONV_TALL=0 disables.
-        constexpr int tall = 200;
-        if (glds_mode == 16 && tall && wide && stride == 1 && tap_mask == 0x1ff && out_scale == 1 && Ho >= tall)
+        // (half as many workgroups: tail effects) and on the HBM-bound 1216^2 layers.
+        if (wide && tap_mask == 0x1ff && out_scale == 1 && Ho >= 200)
             return launch_conv_glds<64, 16, 1, 3, 16>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, 1, 0, 0, stream, 1, Rz, 0, nslot);
-        if (glds_mode == 16)
-            return wide ? launch_conv_glds<64, 16>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot)
-                        : launch_conv_glds<32, 16>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot);
-        return wide ? launch_conv_glds<64, 32>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot)
-                    : launch_conv_glds<32, 32>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot);
+        return wide ? launch_conv_glds<64, 16>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot)
+                    : launch_conv_glds<32, 16>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot);
     }
-    if (Rz) { octa::set_error("octa_conv3x3_nhwc_fwd: the residual is implemented in the DMA-staged kernel only (OCTA_CONV_GLDS=0 is set)"); return -2; }
-    if (nslot) { octa::set_error("octa_conv3x3_nhwc_fwd: statistics slots are implemented in the DMA-staged kernel only (OCTA_CONV_GLDS=0 is set)"); return -2; }
     if (stride == 1) return wide ? launch_conv<64, 1>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, tap_mask, out_scale, out_off_y, out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, stream)
                                  : launch_conv<32, 1>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, tap_mask, out_scale, out_off_y, out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, stream);
     return wide ? launch_conv<64, 2>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, tap_mask, out_scale, out_off_y, out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, stream)
                 : launch_conv<32, 2>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, tap_mask, out_scale, out_off_y, out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, stream);
 }
-}  // namespace
 
-extern "C" int octa_conv3x3_nhwc_fwd6(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2,
-                                      int CY1, int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask,
-                                      int out_scale, int out_off_y, int out_off_x, const float *d_scale1, const float *d_shift1,
-                                      const float *d_scale2, const float *d_shift2, float slope, float *d_stat_partials,
-                                      const void *d_residual, void *stream_) {
-    return conv3x3_fwd_impl(ctx, d_x, d_x2, C1, d_w, d_y, d_y2, CY1, N, H, W, Cin, Cout, stride, in_dilation, tap_mask, out_scale, out_off_y, out_off_x,
-                            d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, d_residual, nullptr, 0, stream_);
-}
-
-// fwd7 = fwd2 + the InstanceNorm statistics of the RESULT in slot form (round 5): d_stat_slots is double[nslot][N][Cout][2], zero on entry;
-// every output tile adds the sum and the sum of squares of its bf16-rounded results per channel to slot (tile % nslot). Replaces the
-// statistics pass of the norm layer that follows (reference: MONAI UnetBasicBlock conv -> InstanceNorm, models/networks.py:6);
-// octa_instnorm_lrelu_nhwc_fwd_s consumes the slots. Plain single output, stride 1 or 2, no input dilation mask restrictions beyond fwd2's.
-extern "C" int octa_conv3x3_nhwc_fwd7(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, int N, int H, int W,
-                                      int Cin, int Cout, int stride, double *d_stat_slots, int nslot, void *stream_) {
-    if (!d_stat_slots) { octa::set_error("octa_conv3x3_nhwc_fwd7: null statistics slots"); return -2; }
-    return conv3x3_fwd_impl(ctx, d_x, d_x2, C1, d_w, d_y, nullptr, Cout, N, H, W, Cin, Cout, stride, 1, 0x1ff, 1, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                            0.f, nullptr, nullptr, d_stat_slots, nslot, stream_);
-}
-
-extern "C" int octa_conv3x3_nhwc_fwd5(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2,
-                                      int CY1, int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask,
-                                      int out_scale, int out_off_y, int out_off_x, const float *d_scale1, const float *d_shift1,
-                                      const float *d_scale2, const float *d_shift2, float slope, float *d_stat_partials, void *stream_) {
-    return octa_conv3x3_nhwc_fwd6(ctx, d_x, d_x2, C1, d_w, d_y, d_y2, CY1, N, H, W, Cin, Cout, stride, in_dilation, tap_mask, out_scale, out_off_y,
-                                  out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, nullptr, stream_);
-}
-
-extern "C" int octa_conv3x3_nhwc_fwd4(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2,
-                                      int CY1, int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask,
-                                      int out_scale, int out_off_y, int out_off_x, const float *d_scale1, const float *d_shift1,
-                                      const float *d_scale2, const float *d_shift2, float slope, void *stream_) {
-    return octa_conv3x3_nhwc_fwd5(ctx, d_x, d_x2, C1, d_w, d_y, d_y2, CY1, N, H, W, Cin, Cout, stride, in_dilation, tap_mask, out_scale, out_off_y,
-                                  out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, nullptr, stream_);
-}
-
-extern "C" int octa_conv3x3_nhwc_fwd3(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2,
-                                      int CY1, int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask,
-                                      int out_scale, int out_off_y, int out_off_x, void *stream_) {
-    return octa_conv3x3_nhwc_fwd4(ctx, d_x, d_x2, C1, d_w, d_y, d_y2, CY1, N, H, W, Cin, Cout, stride, in_dilation, tap_mask, out_scale, out_off_y,
-                                  out_off_x, nullptr, nullptr, nullptr, nullptr, 0.f, stream_);
-}
-
-extern "C" int octa_conv3x3_nhwc_fwd2(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_w, void *d_y, void *d_y2,
-                                      int CY1, int N, int H, int W, int Cin, int Cout, int stride, int in_dilation, int tap_mask,
-                                      void *stream_) {
-    return octa_conv3x3_nhwc_fwd3(ctx, d_x, d_x2, C1, d_w, d_y, d_y2, CY1, N, H, W, Cin, Cout, stride, in_dilation, tap_mask, 1, 0, 0, stream_);
-}
-
-extern "C" int octa_conv3x3_nhwc_fwd(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin,
-                                     int Cout, int stride, int in_dilation, void *stream_) {
-    return octa_conv3x3_nhwc_fwd2(ctx, d_x, nullptr, Cin, d_w, d_y, nullptr, Cout, N, H, W, Cin, Cout, stride, in_dilation, 0x1ff, stream_);
-}
-
-// d_x [N][H][W][Cin] bf16 (the SMALL image), d_w [9][Cout][Cin] bf16 packed as for the zero-insertion form (octa_conv3x3_nhwc_fwd2 with
+// d_x [N][H][W][Cin] bf16 (the SMALL image), d_w [9][Cout][Cin] bf16 packed as for the zero-insertion form (octa_conv3x3_nhwc_fwd with
 // in_dilation = 2 gives the same result: tests/test_conv_gpu.py), d_y [N][2H][2W][Cout] bf16; tap_mask as there (0x1ff: data gradient of a
-// stride-2 3x3 layer; 0b000011011: the 2x2 stride-2 transposed convolution); d_residual (shape of d_y, may be NULL) is added as in _fwd6.
+// stride-2 3x3 layer; 0b000011011: the 2x2 stride-2 transposed convolution); d_residual (shape of d_y, may be NULL) is added as octa_conv3x3_nhwc_fwd adds it.
 extern "C" int octa_conv3x3_s2t_nhwc(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int tap_mask,
                                      const void *d_residual, void *stream_) {
     if (!ctx || !d_x || !d_w || !d_y) { octa::set_error("octa_conv3x3_s2t_nhwc: null pointer"); return -2; }
@@ -988,20 +935,13 @@ extern "C" int octa_conv4x4_nhwc_fwd(octa_ctx *ctx, const void *d_x, const void 
 // 3 x 3 convolution, stride 1, with an explicit padding: pad = 0 (valid), 1 (same) or 2 (full: what the data gradient of a valid
 // convolution is), zeros outside the image -- or, reflect = 1 with pad = 1, nn.ReflectionPad2d(1) fused into the halo fetch (the
 // ResNet blocks of the generator, models/networks.py:_resblock_nhwc: no padded copy, no cropped copy). Output (H + 2 pad - 2)^2.
-extern "C" int octa_conv3x3_nhwc_fwd_pad_s(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int pad,
-                                           int reflect, double *d_stat_slots, int nslot, void *stream_);
+// d_stat_slots (NULL = none): the InstanceNorm statistics of the result accumulated by the epilogue in slot form (double [nslot][N][Cout][2],
+// zeroed by the caller; as octa_conv3x3_nhwc_fwd): the generator's residual blocks are reflect-padded convolution -> InstanceNorm, 18 of
+// them per pass, and each paid a statistics launch over a tensor that had just been written.
 extern "C" int octa_conv3x3_nhwc_fwd_pad(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int pad,
-                                         int reflect, void *stream_) {
-    return octa_conv3x3_nhwc_fwd_pad_s(ctx, d_x, d_w, d_y, N, H, W, Cin, Cout, pad, reflect, nullptr, 0, stream_);
-}
-
-// ... with the InstanceNorm statistics of the result accumulated by the epilogue in slot form (d_stat_slots: double [nslot][N][Cout][2], zeroed by
-// the caller; as octa_conv3x3_nhwc_fwd7): the generator's residual blocks are reflect-padded convolution -> InstanceNorm, 18 of them per pass,
-// and each paid a statistics launch over a tensor that had just been written (round 5). NULL slots = octa_conv3x3_nhwc_fwd_pad.
-extern "C" int octa_conv3x3_nhwc_fwd_pad_s(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int pad,
-                                           int reflect, double *d_stat_slots, int nslot, void *stream_) {
+                                         int reflect, double *d_stat_slots, int nslot, void *stream_) {
     if (!ctx || !d_x || !d_w || !d_y) { octa::set_error("octa_conv3x3_nhwc_fwd_pad: null pointer"); return -2; }
-    if (d_stat_slots && (nslot <= 0 || nslot > 1024)) { octa::set_error("octa_conv3x3_nhwc_fwd_pad_s: statistics slots need 1..1024 slots"); return -2; }
+    if (d_stat_slots && (nslot <= 0 || nslot > 1024)) { octa::set_error("octa_conv3x3_nhwc_fwd_pad: statistics slots need 1..1024 slots"); return -2; }
     if (!d_stat_slots) nslot = 0;
     float *part = reinterpret_cast<float *>(d_stat_slots);      // one kernel argument: read as double slots when nslot > 0
     if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || pad < 0 || pad > 2 || H + 2 * pad < 3 || W + 2 * pad < 3) { octa::set_error("octa_conv3x3_nhwc_fwd_pad: bad shape"); return -2; }
@@ -1626,11 +1566,21 @@ int launch_wgrad(const unsigned short *X, const unsigned short *X2, int C1, cons
 
 }  // namespace
 
-// acc: d_dw is a gradient buffer in the PARAMETER layout [Cout][Cin][3][3] that receives the result ADDED to its contents (wgrad_tr_acc_kernel)
-static int wgrad4_impl(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_dy, float *d_dw, int N, int H,
-                       int W, int Cin, int Cout, int stride, int tap_mask, const float *d_scale1, const float *d_shift1,
-                       const float *d_scale2, const float *d_shift2, float slope, void *stream_, int acc /* 0: d_dw [9][Cout][Cin]; 1: add to / 2: overwrite a parameter-layout buffer */) {
+// The one 3x3 weight-gradient entry point (include/octa_hip.h: octa_conv3x3_wgrad_args). out_mode OCTA_WGRAD_TAP_MAJOR: d_dw is
+// [9][Cout][Cin], overwritten; OCTA_WGRAD_PARAM_ADD / OCTA_WGRAD_PARAM_SET: d_dw is a gradient buffer in the PARAMETER layout
+// [Cout][Cin][3][3] (models/networks.py / MONAI state-dict layout: what the training step's `weight.grad` is) that receives the result
+// added to its contents / written over them (wgrad_tr_acc_kernel); taps outside tap_mask contribute zero.
+extern "C" int octa_conv3x3_nhwc_wgrad(octa_ctx *ctx, const octa_conv3x3_wgrad_args *a, void *stream_) {
+    if (!a) { octa::set_error("octa_conv3x3_nhwc_wgrad: null pointer"); return -2; }
+    if (a->struct_size != sizeof(octa_conv3x3_wgrad_args)) { octa::set_error("octa_conv3x3_nhwc_wgrad: struct_size %u, this library's octa_conv3x3_wgrad_args has %zu bytes", a->struct_size, sizeof(octa_conv3x3_wgrad_args)); return -2; }
+    const void *d_x = a->d_x, *d_x2 = a->d_x2, *d_dy = a->d_dy;
+    float *d_dw = a->d_dw;
+    int C1 = a->C1, tap_mask = a->tap_mask;
+    const int N = a->N, H = a->H, W = a->W, Cin = a->Cin, Cout = a->Cout, stride = a->stride, out_mode = a->out_mode;
+    const float *d_scale1 = a->d_scale1, *d_shift1 = a->d_shift1, *d_scale2 = a->d_scale2, *d_shift2 = a->d_shift2;
+    const float slope = a->slope;
     if (!ctx || !d_x || !d_dy || !d_dw) { octa::set_error("octa_conv3x3_nhwc_wgrad: null pointer"); return -2; }
+    if (out_mode < OCTA_WGRAD_TAP_MAJOR || out_mode > OCTA_WGRAD_PARAM_SET) { octa::set_error("octa_conv3x3_nhwc_wgrad: out_mode %d is none of OCTA_WGRAD_*", out_mode); return -2; }
     tap_mask &= 0x1ff;
     if (tap_mask == 0) { octa::set_error("octa_conv3x3_nhwc_wgrad: empty tap mask"); return -2; }
     if (N <= 0 || H <= 0 || W <= 0) { octa::set_error("octa_conv3x3_nhwc_wgrad: bad shape"); return -2; }
@@ -1644,21 +1594,18 @@ static int wgrad4_impl(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1,
     const unsigned short *z = zero_page(ctx);
     if (!z) return -1;
     const bool co64 = Cout % 64 == 0, ci64 = Cin % 64 == 0 && C1 % 64 == 0;   // a 64-channel block must not straddle the split
-    constexpr int use_tr = 2;           // transposing-read weight-gradient kernels at stride 1 and 2 (the round-3/4 switch OCTA_WGRAD_TR is gone)
-    if (use_tr && !d_scale1 && !d_scale2 && (stride == 1 || (stride == 2 && H % 2 == 0 && W % 2 == 0))) {
-        // raw tiles + transposing reads (see conv3x3_nhwc_wgrad_tr_kernel); OCTA_WGRAD_TR=1: stride 1 only, =2 (default): stride 2 as well
+    if (!d_scale1 && !d_scale2 && (stride == 1 || (stride == 2 && H % 2 == 0 && W % 2 == 0))) {
+        // raw tiles + transposing reads (see conv3x3_nhwc_wgrad_tr_kernel)
         if (stride == 1) {
-            if (co64 && ci64) return launch_wgrad_tr<64, 64>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, acc ? d_dw : nullptr, acc == 1);
-            if (co64) return launch_wgrad_tr<64, 32>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, acc ? d_dw : nullptr, acc == 1);
-            if (ci64) return launch_wgrad_tr<32, 64>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, acc ? d_dw : nullptr, acc == 1);
-            return launch_wgrad_tr<32, 32>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, acc ? d_dw : nullptr, acc == 1);
+            if (co64 && ci64) return launch_wgrad_tr<64, 64>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
+            if (co64) return launch_wgrad_tr<64, 32>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
+            if (ci64) return launch_wgrad_tr<32, 64>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
+            return launch_wgrad_tr<32, 32>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
         }
-        if (use_tr >= 2) {
-            if (co64) return launch_wgrad_tr<64, 32, 2>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, acc ? d_dw : nullptr, acc == 1);
-            return launch_wgrad_tr<32, 32, 2>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, acc ? d_dw : nullptr, acc == 1);
-        }
+        if (co64) return launch_wgrad_tr<64, 32, 2>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
+        return launch_wgrad_tr<32, 32, 2>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
     }
-    if (acc) { octa::set_error("octa_conv3x3_nhwc_wgrad_acc: needs the transposing-read kernels (no normalise-on-load operands, OCTA_WGRAD_TR unset, even sizes at stride 2)"); return -2; }
+    if (out_mode) { octa::set_error("octa_conv3x3_nhwc_wgrad: the parameter-layout output needs the transposing-read kernels (no normalise-on-load operands, even sizes at stride 2)"); return -2; }
     OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 9 * (size_t)Cout * Cin, stream));
     if (stride == 2) {
         if (H % 2 || W % 2) { octa::set_error("octa_conv3x3_nhwc_wgrad: stride-2 layers need even input sizes"); return -2; }
@@ -1673,25 +1620,12 @@ static int wgrad4_impl(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1,
     return launch_wgrad<32, 32>(X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, d_scale1, d_shift1, d_scale2, d_shift2, slope, z, stream);
 }
 
-extern "C" int octa_conv3x3_nhwc_wgrad4(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_dy, float *d_dw, int N, int H,
-                                        int W, int Cin, int Cout, int stride, int tap_mask, const float *d_scale1, const float *d_shift1,
-                                        const float *d_scale2, const float *d_shift2, float slope, void *stream_) {
-    return wgrad4_impl(ctx, d_x, d_x2, C1, d_dy, d_dw, N, H, W, Cin, Cout, stride, tap_mask, d_scale1, d_shift1, d_scale2, d_shift2, slope, stream_, 0);
-}
-
-// octa_conv3x3_nhwc_wgrad4 (no normalise-on-load operands) with the result ADDED to d_grad in the parameter's own layout, float32
-// [Cout][Cin][3][3] (models/networks.py / MONAI state-dict layout): what the training step's `weight.grad` is (accumulate = 0: overwritten
-// instead). Taps outside tap_mask contribute zero.
-extern "C" int octa_conv3x3_nhwc_wgrad_acc(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_dy, float *d_grad, int N, int H,
-                                           int W, int Cin, int Cout, int stride, int tap_mask, int accumulate, void *stream_) {
-    return wgrad4_impl(ctx, d_x, d_x2, C1, d_dy, d_grad, N, H, W, Cin, Cout, stride, tap_mask, nullptr, nullptr, nullptr, nullptr, 0.f, stream_, accumulate ? 1 : 2);
-}
-
 // Weight gradient of octa_conv3x3_nhwc_fwd_pad: d_x [N][H][W][Cin], d_dy [N][H + 2 pad - 2][W + 2 pad - 2][Cout], stride 1; reflect = 1
-// (pad = 1): the input was mirrored at its borders (nn.ReflectionPad2d(1) in front of the convolution).
-static int wgrad_pad_impl(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cin, int Cout, int pad,
-                          int reflect, void *stream_, int acc) {
+// (pad = 1): the input was mirrored at its borders (nn.ReflectionPad2d(1) in front of the convolution). out_mode as octa_conv3x3_nhwc_wgrad.
+extern "C" int octa_conv3x3_nhwc_wgrad_pad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cin, int Cout, int pad,
+                                           int reflect, int out_mode, void *stream_) {
     if (!ctx || !d_x || !d_dy || !d_dw) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: null pointer"); return -2; }
+    if (out_mode < OCTA_WGRAD_TAP_MAJOR || out_mode > OCTA_WGRAD_PARAM_SET) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: out_mode %d is none of OCTA_WGRAD_*", out_mode); return -2; }
     if (N <= 0 || H <= 0 || W <= 0 || pad < 0 || pad > 2 || H + 2 * pad < 3 || W + 2 * pad < 3) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: bad shape"); return -2; }
     if (reflect && (pad != 1 || H < 2 || W < 2)) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: reflection needs pad = 1 and an image of at least 2 x 2"); return -2; }
     if (Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: Cin and Cout must be multiples of 32 (got %d, %d)", Cin, Cout); return -2; }
@@ -1701,21 +1635,10 @@ static int wgrad_pad_impl(octa_ctx *ctx, const void *d_x, const void *d_dy, floa
     if (!z) return -1;
     const unsigned short *X = static_cast<const unsigned short *>(d_x), *dY = static_cast<const unsigned short *>(d_dy);
     const bool co64 = Cout % 64 == 0, ci64 = Cin % 64 == 0;
-    if (co64 && ci64) return launch_wgrad_tr<64, 64>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, acc ? d_dw : nullptr, acc == 1);
-    if (co64) return launch_wgrad_tr<64, 32>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, acc ? d_dw : nullptr, acc == 1);
-    if (ci64) return launch_wgrad_tr<32, 64>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, acc ? d_dw : nullptr, acc == 1);
-    return launch_wgrad_tr<32, 32>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, acc ? d_dw : nullptr, acc == 1);
-}
-
-extern "C" int octa_conv3x3_nhwc_wgrad_pad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cin, int Cout, int pad,
-                                           int reflect, void *stream_) {
-    return wgrad_pad_impl(ctx, d_x, d_dy, d_dw, N, H, W, Cin, Cout, pad, reflect, stream_, 0);
-}
-
-// octa_conv3x3_nhwc_wgrad_pad with the result ADDED to d_grad in the parameter layout [Cout][Cin][3][3] (see octa_conv3x3_nhwc_wgrad_acc)
-extern "C" int octa_conv3x3_nhwc_wgrad_pad_acc(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_grad, int N, int H, int W, int Cin, int Cout, int pad,
-                                               int reflect, int accumulate, void *stream_) {
-    return wgrad_pad_impl(ctx, d_x, d_dy, d_grad, N, H, W, Cin, Cout, pad, reflect, stream_, accumulate ? 1 : 2);
+    if (co64 && ci64) return launch_wgrad_tr<64, 64>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
+    if (co64) return launch_wgrad_tr<64, 32>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
+    if (ci64) return launch_wgrad_tr<32, 64>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
+    return launch_wgrad_tr<32, 32>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
 }
 
 extern "C" int octa_conv4x4_nhwc_wgrad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cin, int Cout,
@@ -1732,22 +1655,6 @@ extern "C" int octa_conv4x4_nhwc_wgrad(octa_ctx *ctx, const void *d_x, const voi
     if (Cout % 64 == 0 && Cin % 64 == 0)
         return launch_wgrad_impl<64, 64, false, 1, 4>(X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0xffff, nullptr, nullptr, nullptr, nullptr, 0.f, z, stream);
     return launch_wgrad_impl<32, 32, false, 1, 4>(X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0xffff, nullptr, nullptr, nullptr, nullptr, 0.f, z, stream);
-}
-
-extern "C" int octa_conv3x3_nhwc_wgrad3(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_dy, float *d_dw, int N, int H,
-                                        int W, int Cin, int Cout, int tap_mask, const float *d_scale1, const float *d_shift1,
-                                        const float *d_scale2, const float *d_shift2, float slope, void *stream_) {
-    return octa_conv3x3_nhwc_wgrad4(ctx, d_x, d_x2, C1, d_dy, d_dw, N, H, W, Cin, Cout, 1, tap_mask, d_scale1, d_shift1, d_scale2, d_shift2, slope, stream_);
-}
-
-extern "C" int octa_conv3x3_nhwc_wgrad2(octa_ctx *ctx, const void *d_x, const void *d_x2, int C1, const void *d_dy, float *d_dw, int N, int H,
-                                        int W, int Cin, int Cout, int tap_mask, void *stream_) {
-    return octa_conv3x3_nhwc_wgrad3(ctx, d_x, d_x2, C1, d_dy, d_dw, N, H, W, Cin, Cout, tap_mask, nullptr, nullptr, nullptr, nullptr, 0.f, stream_);
-}
-
-extern "C" int octa_conv3x3_nhwc_wgrad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cin,
-                                       int Cout, void *stream_) {
-    return octa_conv3x3_nhwc_wgrad2(ctx, d_x, nullptr, Cin, d_dy, d_dw, N, H, W, Cin, Cout, 0x1ff, stream_);
 }
 
 // ---- 1x1 head with one output channel (UnetOutBlock, 32 -> 1 with bias): HBM-bound streaming kernels ----------
@@ -1820,15 +1727,16 @@ head1_bwd_kernel(const unsigned short *__restrict__ x, const unsigned short *__r
 
 }  // namespace
 
-extern "C" int octa_head1_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, float bias, int64_t npix, int C, void *d_y,
-                                   void *stream_) {
+// d_bias: float32[1] in device memory or NULL (no host read-back of the parameter in the training step)
+extern "C" int octa_head1_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_bias, int64_t npix, int C, void *d_y,
+                                     void *stream_) {
     if (!ctx || !d_x || !d_w || !d_y || npix <= 0 || C <= 0 || C % 8 || C > 256) { octa::set_error("octa_head1_nhwc_fwd: bad arguments (C must be a multiple of 8, <= 256)"); return -2; }
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     long blocks = (npix + 255) / 256;
     if (blocks > 16L * ctx->num_cus) blocks = 16L * ctx->num_cus;
-    hipLaunchKernelGGL(head1_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, static_cast<const unsigned short *>(d_x), d_w, bias,
-                       (const float *)nullptr, (long)npix, C, static_cast<unsigned short *>(d_y));
+    hipLaunchKernelGGL(head1_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, static_cast<const unsigned short *>(d_x), d_w, 0.f, d_bias,
+                       (long)npix, C, static_cast<unsigned short *>(d_y));
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -2049,9 +1957,9 @@ c1_wgrad_reduce_kernel(const float *__restrict__ ws, float *__restrict__ dW, int
 
 }  // namespace
 
-// d_stat / nslot: optional InstanceNorm statistics of the result in slot form (see conv3x3_c1_fwd_kernel; octa_conv3x3_nhwc_fwd7's contract)
-extern "C" int octa_conv3x3_c1_fwd2(octa_ctx *ctx, const void *d_x, const float *d_w, void *d_y, int N, int H, int W, int Cout, double *d_stat,
-                                    int nslot, void *stream_) {
+// d_stat / nslot: optional InstanceNorm statistics of the result in slot form (NULL = none; see conv3x3_c1_fwd_kernel; octa_conv3x3_nhwc_fwd's slot contract)
+extern "C" int octa_conv3x3_c1_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, void *d_y, int N, int H, int W, int Cout, double *d_stat,
+                                   int nslot, void *stream_) {
     if (!ctx || !d_x || !d_w || !d_y || N <= 0 || H <= 0 || W <= 0) { octa::set_error("octa_conv3x3_c1_fwd: bad arguments"); return -2; }
     if (Cout != 8 && Cout != 16 && Cout != 32 && Cout != 64) { octa::set_error("octa_conv3x3_c1_fwd: Cout must be 8, 16, 32 or 64"); return -2; }
     if (W > 3840 || N > 65535) { octa::set_error("octa_conv3x3_c1_fwd: W > 3840 or N > 65535"); return -2; }
@@ -2066,10 +1974,6 @@ extern "C" int octa_conv3x3_c1_fwd2(octa_ctx *ctx, const void *d_x, const float 
                        static_cast<const unsigned short *>(d_x), d_w, static_cast<unsigned short *>(d_y), H, W, Cout, d_stat, nslot, band);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
-}
-
-extern "C" int octa_conv3x3_c1_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, void *d_y, int N, int H, int W, int Cout, void *stream_) {
-    return octa_conv3x3_c1_fwd2(ctx, d_x, d_w, d_y, N, H, W, Cout, nullptr, 0, stream_);
 }
 
 extern "C" int octa_conv3x3_c1_wgrad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cout, void *stream_) {
@@ -2146,20 +2050,6 @@ extern "C" int octa_pack_conv_weights(octa_ctx *ctx, const int64_t *d_table, int
     // 256 workgroups per layer: the launch lasts as long as the largest layer's share (512 x 512 x 9: 85 us with 64 workgroups on it, one per step)
     hipLaunchKernelGGL(pack_weights_kernel, dim3(256, (unsigned)L), dim3(256), 0, stream, reinterpret_cast<const long *>(d_table),
                        static_cast<unsigned short *>(d_dst));
-    OCTA_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// head forward with the bias read from device memory (no host read-back of the parameter in the training step)
-extern "C" int octa_head1_nhwc_fwd_b(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_bias, int64_t npix, int C, void *d_y,
-                                     void *stream_) {
-    if (!ctx || !d_x || !d_w || !d_y || npix <= 0 || C <= 0 || C % 8 || C > 256) { octa::set_error("octa_head1_nhwc_fwd_b: bad arguments (C must be a multiple of 8, <= 256)"); return -2; }
-    hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    long blocks = (npix + 255) / 256;
-    if (blocks > 16L * ctx->num_cus) blocks = 16L * ctx->num_cus;
-    hipLaunchKernelGGL(head1_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, static_cast<const unsigned short *>(d_x), d_w, 0.f, d_bias,
-                       (long)npix, C, static_cast<unsigned short *>(d_y));
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -403,7 +403,7 @@ in_nhwc_fwd_apply(const unsigned short *__restrict__ x, unsigned short *__restri
     __shared__ float s_g[NHWC_MAXC], s_sh[NHWC_MAXC];
     const int b = blockIdx.y + b0, s = blockIdx.x;
     for (int c = threadIdx.x; c < C; c += NT) {
-        // nslot > 1: the sums come from the producing convolution's epilogue, spread over slots [nslot][B][C][2] (csrc/conv.hip, fwd7)
+        // nslot > 1: the sums come from the producing convolution's epilogue, spread over slots [nslot][B][C][2] (csrc/conv.hip, octa_conv3x3_nhwc_fwd)
         double sa, sq;
         slot_sum(sums, (long)b * C + c, nslot, slot_stride, sa, sq);
         const double mean_d = sa / (double)hw;
@@ -551,64 +551,6 @@ int nhwc_check(const char *who, int B, int C, int64_t hw) {
 
 }  // namespace
 
-extern "C" int octa_instnorm_lrelu_nhwc_fwd(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_w, const float *d_b,
-                                            float *d_mean, float *d_rstd, int B, int C, int64_t hw, float slope, float eps,
-                                            void *stream_) {
-    if (!ctx || !d_x || !d_y || !d_mean || !d_rstd) { octa::set_error("octa_instnorm_lrelu_nhwc_fwd: null pointer"); return -2; }
-    if (nhwc_check("octa_instnorm_lrelu_nhwc_fwd", B, C, hw)) return -2;
-    hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));   // pre-zeroed ring slot
-    if (!sums) return -1;
-    // optional image groups (nhwc_group): statistics and application of one group back to back
-    const int group = nhwc_group(B, (size_t)hw * C * 2);
-    const int splits = nhwc_splits(ctx, group, hw);
-    dim3 grid((unsigned)splits, (unsigned)group);
-    const unsigned short *x = static_cast<const unsigned short *>(d_x);
-    for (int b0 = 0; b0 < B; b0 += group) {
-        if (b0 + group > B) grid.y = (unsigned)(B - b0);
-        hipLaunchKernelGGL(in_nhwc_stats<0>, grid, dim3(NT), 0, stream, x, (const unsigned short *)nullptr, d_w, d_b, (const float *)nullptr,
-                           (const float *)nullptr, (long)hw, C, splits, slope, sums, b0);
-        hipLaunchKernelGGL(in_nhwc_fwd_apply, grid, dim3(NT), 0, stream, x, static_cast<unsigned short *>(d_y), d_w, d_b, (long)hw, C, splits,
-                           sums, slope, eps, d_mean, d_rstd, b0);
-    }
-    OCTA_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int octa_instnorm_lrelu_nhwc_bwd(octa_ctx *ctx, const void *d_x, const void *d_dy, const float *d_w, const float *d_b,
-                                            const float *d_mean, const float *d_rstd, void *d_dx, float *d_dw, float *d_db, int B,
-                                            int C, int64_t hw, float slope, void *stream_) {
-    if (!ctx || !d_x || !d_dy || !d_dx || !d_mean || !d_rstd) { octa::set_error("octa_instnorm_lrelu_nhwc_bwd: null pointer"); return -2; }
-    if (nhwc_check("octa_instnorm_lrelu_nhwc_bwd", B, C, hw)) return -2;
-    hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));   // pre-zeroed ring slot
-    if (!sums) return -1;
-    const int group = nhwc_group(B, (size_t)hw * C * 2 * 2);   // two tensors (x, dy) are read twice
-    const int bsum = group == B ? B : 0;                         // one launch covers the batch: gradients are stored, not accumulated
-    if (!bsum) {
-        if (d_dw && d_db == d_dw + C) {                               // allocated back to back by the host side: one fill
-            OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 2 * C, stream));
-        } else {
-            if (d_dw) OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * C, stream));
-            if (d_db) OCTA_HIP_CHECK(hipMemsetAsync(d_db, 0, sizeof(float) * C, stream));
-        }
-    }
-    const int splits = nhwc_splits(ctx, group, hw);
-    dim3 grid((unsigned)splits, (unsigned)group);
-    const unsigned short *x = static_cast<const unsigned short *>(d_x), *dy = static_cast<const unsigned short *>(d_dy);
-    for (int b0 = 0; b0 < B; b0 += group) {
-        if (b0 + group > B) grid.y = (unsigned)(B - b0);
-        hipLaunchKernelGGL(in_nhwc_stats<1>, grid, dim3(NT), 0, stream, x, dy, d_w, d_b, d_mean, d_rstd, (long)hw, C, splits, slope, sums, b0);
-        hipLaunchKernelGGL(in_nhwc_bwd_apply, grid, dim3(NT), 0, stream, x, dy, static_cast<unsigned short *>(d_dx), d_w, d_b, d_mean, d_rstd,
-                           (long)hw, C, splits, slope, sums, d_dw, d_db, b0, bsum);
-    }
-    OCTA_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// ---- statistics only + lazy application (normalise-on-load path of csrc/conv.hip) ---------------------------------
 namespace {
 
 __global__ void __launch_bounds__(NT)
@@ -683,7 +625,7 @@ extern "C" int octa_scale_shift_lrelu_nhwc(octa_ctx *ctx, const void *d_x, void 
     return 0;
 }
 
-// ---- forward with the statistics already accumulated by the producing convolution (csrc/conv.hip, _fwd5) ----------
+// ---- forward, optionally with the statistics already accumulated by the producing convolution (csrc/conv.hip) ----------
 namespace {
 
 // partials [B][tiles][C][2] float -> sums [B][C][2] double. Block = 8 tile lanes x 32 channels.
@@ -707,40 +649,85 @@ in_nhwc_fold_partials(const float *__restrict__ part, int tiles, int C, double *
 
 }  // namespace
 
-extern "C" int octa_instnorm_lrelu_nhwc_fwd_p(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_w, const float *d_b, float *d_mean,
-                                              float *d_rstd, int B, int C, int64_t hw, float slope, float eps, const float *d_partials,
-                                              int tiles, void *stream_) {
-    if (!ctx || !d_x || !d_y || !d_mean || !d_rstd || !d_partials || tiles <= 0) { octa::set_error("octa_instnorm_lrelu_nhwc_fwd_p: bad arguments"); return -2; }
-    if (nhwc_check("octa_instnorm_lrelu_nhwc_fwd_p", B, C, hw)) return -2;
+// Statistics source: none of the two = a statistics pass of its own over d_x; d_stat_partials = the per-tile float partials [B][tiles][C][2] of
+// the convolution that wrote x (folded here, then applied); d_stat_slots = the same sums in slot form, double [nslot][B][C][2], accumulated by that
+// convolution's epilogue (octa_conv3x3_nhwc_fwd, _fwd_pad, octa_conv3x3_c1_fwd): one launch, the apply pass adds the slots up while it derives
+// scale / shift. Both at once are refused.
+extern "C" int octa_instnorm_lrelu_nhwc_fwd(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_w, const float *d_b, float *d_mean,
+                                            float *d_rstd, int B, int C, int64_t hw, float slope, float eps, const float *d_stat_partials,
+                                            int tiles, const double *d_stat_slots, int nslot, void *stream_) {
+    if (!ctx || !d_x || !d_y || !d_mean || !d_rstd) { octa::set_error("octa_instnorm_lrelu_nhwc_fwd: null pointer"); return -2; }
+    if ((d_stat_partials && (d_stat_slots || tiles <= 0)) || (d_stat_slots && (nslot <= 0 || nslot > 1024))) {
+        octa::set_error("octa_instnorm_lrelu_nhwc_fwd: one statistics source at most, with tiles >= 1 or 1..1024 slots");
+        return -2;
+    }
+    if (nhwc_check("octa_instnorm_lrelu_nhwc_fwd", B, C, hw)) return -2;
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    if (ctx->r_tile_total.reserve(sizeof(double) * 2 * (size_t)B * C)) return -1;
-    double *sums = ctx->r_tile_total.as<double>();
-    hipLaunchKernelGGL(in_nhwc_fold_partials, dim3((unsigned)((C + 31) / 32), (unsigned)B), dim3(NT), 0, stream, d_partials, tiles, C, sums);
-    const int splits = nhwc_splits(ctx, B, hw);
-    hipLaunchKernelGGL(in_nhwc_fwd_apply, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, static_cast<const unsigned short *>(d_x),
-                       static_cast<unsigned short *>(d_y), d_w, d_b, (long)hw, C, splits, sums, slope, eps, d_mean, d_rstd, 0);
+    const unsigned short *x = static_cast<const unsigned short *>(d_x);
+    unsigned short *y = static_cast<unsigned short *>(d_y);
+    if (d_stat_slots) {
+        const int splits = nhwc_splits(ctx, B, hw);
+        hipLaunchKernelGGL(in_nhwc_fwd_apply, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, x, y, d_w, d_b, (long)hw, C, splits, d_stat_slots,
+                           slope, eps, d_mean, d_rstd, 0, nslot, (long)B * C * 2);
+    } else if (d_stat_partials) {
+        if (ctx->r_tile_total.reserve(sizeof(double) * 2 * (size_t)B * C)) return -1;
+        double *sums = ctx->r_tile_total.as<double>();
+        hipLaunchKernelGGL(in_nhwc_fold_partials, dim3((unsigned)((C + 31) / 32), (unsigned)B), dim3(NT), 0, stream, d_stat_partials, tiles, C, sums);
+        const int splits = nhwc_splits(ctx, B, hw);
+        hipLaunchKernelGGL(in_nhwc_fwd_apply, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, x, y, d_w, d_b, (long)hw, C, splits, sums, slope,
+                           eps, d_mean, d_rstd, 0);
+    } else {
+        double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));   // pre-zeroed ring slot
+        if (!sums) return -1;
+        // optional image groups (nhwc_group): statistics and application of one group back to back
+        const int group = nhwc_group(B, (size_t)hw * C * 2);
+        const int splits = nhwc_splits(ctx, group, hw);
+        dim3 grid((unsigned)splits, (unsigned)group);
+        for (int b0 = 0; b0 < B; b0 += group) {
+            if (b0 + group > B) grid.y = (unsigned)(B - b0);
+            hipLaunchKernelGGL(in_nhwc_stats<0>, grid, dim3(NT), 0, stream, x, (const unsigned short *)nullptr, d_w, d_b, (const float *)nullptr,
+                               (const float *)nullptr, (long)hw, C, splits, slope, sums, b0);
+            hipLaunchKernelGGL(in_nhwc_fwd_apply, grid, dim3(NT), 0, stream, x, y, d_w, d_b, (long)hw, C, splits, sums, slope, eps, d_mean, d_rstd, b0);
+        }
+    }
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-// Forward with the statistics in SLOT form (round 5): sums double[nslot][B][C][2] accumulated by the epilogue of the convolution that wrote
-// x (octa_conv3x3_nhwc_fwd7). One launch: the apply pass adds the slots up while it derives scale / shift.
-extern "C" int octa_instnorm_lrelu_nhwc_fwd_s(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_w, const float *d_b, float *d_mean,
-                                              float *d_rstd, int B, int C, int64_t hw, float slope, float eps, const double *d_stat_slots,
-                                              int nslot, void *stream_) {
-    if (!ctx || !d_x || !d_y || !d_mean || !d_rstd || !d_stat_slots || nslot <= 0 || nslot > 1024) { octa::set_error("octa_instnorm_lrelu_nhwc_fwd_s: bad arguments"); return -2; }
-    if (nhwc_check("octa_instnorm_lrelu_nhwc_fwd_s", B, C, hw)) return -2;
+extern "C" int octa_instnorm_lrelu_nhwc_bwd(octa_ctx *ctx, const void *d_x, const void *d_dy, const float *d_w, const float *d_b,
+                                            const float *d_mean, const float *d_rstd, void *d_dx, float *d_dw, float *d_db, int B,
+                                            int C, int64_t hw, float slope, void *stream_) {
+    if (!ctx || !d_x || !d_dy || !d_dx || !d_mean || !d_rstd) { octa::set_error("octa_instnorm_lrelu_nhwc_bwd: null pointer"); return -2; }
+    if (nhwc_check("octa_instnorm_lrelu_nhwc_bwd", B, C, hw)) return -2;
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    const int splits = nhwc_splits(ctx, B, hw);
-    hipLaunchKernelGGL(in_nhwc_fwd_apply, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, static_cast<const unsigned short *>(d_x),
-                       static_cast<unsigned short *>(d_y), d_w, d_b, (long)hw, C, splits, d_stat_slots, slope, eps, d_mean, d_rstd, 0, nslot,
-                       (long)B * C * 2);
+    double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));   // pre-zeroed ring slot
+    if (!sums) return -1;
+    const int group = nhwc_group(B, (size_t)hw * C * 2 * 2);   // two tensors (x, dy) are read twice
+    const int bsum = group == B ? B : 0;                         // one launch covers the batch: gradients are stored, not accumulated
+    if (!bsum) {
+        if (d_dw && d_db == d_dw + C) {                               // allocated back to back by the host side: one fill
+            OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 2 * C, stream));
+        } else {
+            if (d_dw) OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * C, stream));
+            if (d_db) OCTA_HIP_CHECK(hipMemsetAsync(d_db, 0, sizeof(float) * C, stream));
+        }
+    }
+    const int splits = nhwc_splits(ctx, group, hw);
+    dim3 grid((unsigned)splits, (unsigned)group);
+    const unsigned short *x = static_cast<const unsigned short *>(d_x), *dy = static_cast<const unsigned short *>(d_dy);
+    for (int b0 = 0; b0 < B; b0 += group) {
+        if (b0 + group > B) grid.y = (unsigned)(B - b0);
+        hipLaunchKernelGGL(in_nhwc_stats<1>, grid, dim3(NT), 0, stream, x, dy, d_w, d_b, d_mean, d_rstd, (long)hw, C, splits, slope, sums, b0);
+        hipLaunchKernelGGL(in_nhwc_bwd_apply, grid, dim3(NT), 0, stream, x, dy, static_cast<unsigned short *>(d_dx), d_w, d_b, d_mean, d_rstd,
+                           (long)hw, C, splits, slope, sums, d_dw, d_db, b0, bsum);
+    }
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
+// ---- statistics only + lazy application (normalise-on-load path of csrc/conv.hip) ---------------------------------
 // ---- last layer of the U-Net fused: InstanceNorm(affine) + LeakyReLU + 1x1 convolution to ONE channel ---------------
 // DynUNet's last UnetBasicBlock norm followed by UnetOutBlock (MONAI, models/networks.py:6; 32 -> 1 at 1216^2). Unfused, the
 // normalised tensor y (378 MB at B = 4) is written by the norm, read by the head, its gradient is written by the head's backward
@@ -759,7 +746,7 @@ in_nhwc_head_fwd(const unsigned short *__restrict__ x, const float *__restrict__
     __shared__ float s_g[NHWC_MAXC], s_sh[NHWC_MAXC];
     const int b = blockIdx.y, s = blockIdx.x;
     for (int c = threadIdx.x; c < C; c += NT) {
-        double sa, sq;                                   // nslot > 1: from the producing convolution's epilogue (octa_conv3x3_nhwc_fwd7)
+        double sa, sq;                                   // nslot > 1: from the producing convolution's epilogue (octa_conv3x3_nhwc_fwd)
         slot_sum(sums, (long)b * C + c, nslot, slot_stride, sa, sq);
         const double mean_d = sa / (double)hw;
         double var = sq / (double)hw - mean_d * mean_d;
@@ -958,38 +945,29 @@ int head_check(const char *who, int B, int C, int64_t hw) {
 
 }  // namespace
 
+// d_slots (NULL = a statistics pass of its own): the statistics of d_x in slot form, double [nslot][B][C][2], from the convolution that wrote it
+// (octa_conv3x3_nhwc_fwd's d_stat_slots): no statistics pass over the 1216^2 x 32 tensor in front of the head.
 extern "C" int octa_instnorm_lrelu_head1_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_b, const float *d_head_w,
                                                   const float *d_head_b, float *d_mean, float *d_rstd, void *d_logits, int B, int C, int64_t hw,
-                                                  float slope, float eps, void *stream_) {
-    if (!ctx || !d_x || !d_head_w || !d_mean || !d_rstd || !d_logits) { octa::set_error("octa_instnorm_lrelu_head1_nhwc_fwd: null pointer"); return -2; }
+                                                  float slope, float eps, const double *d_slots, int nslot, void *stream_) {
+    if (!ctx || !d_x || !d_head_w || !d_mean || !d_rstd || !d_logits || (d_slots && nslot <= 0)) { octa::set_error("octa_instnorm_lrelu_head1_nhwc_fwd: null pointer"); return -2; }
     if (head_check("octa_instnorm_lrelu_head1_nhwc_fwd", B, C, hw)) return -2;
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));
-    if (!sums) return -1;
     const int splits = nhwc_splits(ctx, B, hw);
     const dim3 grid((unsigned)splits, (unsigned)B);
     const unsigned short *x = static_cast<const unsigned short *>(d_x);
-    hipLaunchKernelGGL(in_nhwc_stats<0>, grid, dim3(NT), 0, stream, x, (const unsigned short *)nullptr, d_w, d_b, (const float *)nullptr,
-                       (const float *)nullptr, (long)hw, C, splits, slope, sums, 0);
-    hipLaunchKernelGGL(in_nhwc_head_fwd, grid, dim3(NT), 0, stream, x, d_w, d_b, (long)hw, C, splits, sums, slope, eps, d_mean, d_rstd, d_head_w,
-                       d_head_b, static_cast<unsigned short *>(d_logits));
-    OCTA_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// The same layer with the statistics of d_x supplied in slot form by the convolution that wrote it (octa_conv3x3_nhwc_fwd7's d_stat_slots,
-// double [nslot][B][C][2]): no statistics pass over the 1216^2 x 32 tensor in front of the head.
-extern "C" int octa_instnorm_lrelu_head1_nhwc_fwd_s(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_b, const float *d_head_w,
-                                                    const float *d_head_b, float *d_mean, float *d_rstd, void *d_logits, int B, int C, int64_t hw,
-                                                    float slope, float eps, const double *d_slots, int nslot, void *stream_) {
-    if (!ctx || !d_x || !d_head_w || !d_mean || !d_rstd || !d_logits || !d_slots || nslot <= 0) { octa::set_error("octa_instnorm_lrelu_head1_nhwc_fwd_s: null pointer"); return -2; }
-    if (head_check("octa_instnorm_lrelu_head1_nhwc_fwd_s", B, C, hw)) return -2;
-    hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    const int splits = nhwc_splits(ctx, B, hw);
-    hipLaunchKernelGGL(in_nhwc_head_fwd, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, static_cast<const unsigned short *>(d_x), d_w, d_b, (long)hw, C,
-                       splits, d_slots, slope, eps, d_mean, d_rstd, d_head_w, d_head_b, static_cast<unsigned short *>(d_logits), nslot, (long)B * C * 2);
+    if (d_slots) {
+        hipLaunchKernelGGL(in_nhwc_head_fwd, grid, dim3(NT), 0, stream, x, d_w, d_b, (long)hw, C, splits, d_slots, slope, eps, d_mean, d_rstd, d_head_w,
+                           d_head_b, static_cast<unsigned short *>(d_logits), nslot, (long)B * C * 2);
+    } else {
+        double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));
+        if (!sums) return -1;
+        hipLaunchKernelGGL(in_nhwc_stats<0>, grid, dim3(NT), 0, stream, x, (const unsigned short *)nullptr, d_w, d_b, (const float *)nullptr,
+                           (const float *)nullptr, (long)hw, C, splits, slope, sums, 0);
+        hipLaunchKernelGGL(in_nhwc_head_fwd, grid, dim3(NT), 0, stream, x, d_w, d_b, (long)hw, C, splits, sums, slope, eps, d_mean, d_rstd, d_head_w,
+                           d_head_b, static_cast<unsigned short *>(d_logits));
+    }
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -16,11 +16,51 @@ def _pad32(c):
     return (c + 31) // 32 * 32
 
 
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _addr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _conv3x3_fwd(x, wt, y, x2=None, y2=None, stride=1, in_dilation=1, tap_mask=0x1ff, scatter=(1, 0, 0), norm=(None, None, None, None), slope=0.0,
+                 stat_partials=None, stat_slots=None, residual=None, what="octa_conv3x3_nhwc_fwd"):
+    """One launch of octa_conv3x3_nhwc_fwd: x (| x2 on the channel axis) [N,H,W,C] -> y (| y2), all bf16; wt packed [9][Cout][Cin]. scatter =
+    (out_scale, out_off_y, out_off_x); norm = (scale1, shift1, scale2, shift2) of the normalise-on-load inputs; stat_partials float32
+    [N][tiles][Cout][2] / stat_slots double [nslot][N][Cout][2] receive the InstanceNorm sums of the result; residual is added in the epilogue."""
+    n, h, w, c1 = x.shape
+    a = _native.Conv3x3Args(
+        struct_size=ctypes.sizeof(_native.Conv3x3Args), N=n, H=h, W=w, Cin=c1 + (x2.shape[3] if x2 is not None else 0),
+        Cout=y.shape[3] + (y2.shape[3] if y2 is not None else 0), stride=int(stride), in_dilation=int(in_dilation), tap_mask=int(tap_mask),
+        out_scale=int(scatter[0]), out_off_y=int(scatter[1]), out_off_x=int(scatter[2]), C1=c1, CY1=y.shape[3],
+        nslot=stat_slots.shape[0] if stat_slots is not None else 0, slope=float(slope), d_x=_addr(x), d_x2=_addr(x2), d_w=_addr(wt), d_y=_addr(y),
+        d_y2=_addr(y2), d_scale1=_addr(norm[0]), d_shift1=_addr(norm[1]), d_scale2=_addr(norm[2]), d_shift2=_addr(norm[3]),
+        d_stat_partials=_addr(stat_partials), d_stat_slots=_addr(stat_slots), d_residual=_addr(residual))
+    _native.check(_native.lib().octa_conv3x3_nhwc_fwd(_native.ctx(x.device.index), ctypes.byref(a), _native.current_stream_ptr()), what)
+
+
+def _conv3x3_wgrad(x1, dy, x2=None, into=None, accumulate=False, stride=1, tap_mask=0x1ff, norm=(None, None, None, None), slope=0.0):
+    """One launch of octa_conv3x3_nhwc_wgrad for the layer with input x1 (| x2 on the channel axis) and output gradient dy. into = None: returns dW
+    [Cout, Cin, 3, 3] float32 (a view of the kernel's tap-major result; taps cleared in tap_mask are zero); into = a float32 gradient buffer in the
+    parameter layout [Cout][Cin][3][3]: the result is added to it (accumulate) or written over it."""
+    n, h, w, c1 = x1.shape
+    cin, cout = c1 + (x2.shape[3] if x2 is not None else 0), dy.shape[3]
+    dw = into if into is not None else torch.empty((9, cout, cin), dtype=torch.float32, device=x1.device)
+    mode = _native.WGRAD_TAP_MAJOR if into is None else (_native.WGRAD_PARAM_ADD if accumulate else _native.WGRAD_PARAM_SET)
+    a = _native.Conv3x3WgradArgs(
+        struct_size=ctypes.sizeof(_native.Conv3x3WgradArgs), N=n, H=h, W=w, Cin=cin, Cout=cout, stride=int(stride), tap_mask=int(tap_mask), C1=c1,
+        out_mode=mode, slope=float(slope), d_x=_addr(x1), d_x2=_addr(x2), d_dy=_addr(dy), d_dw=_addr(dw), d_scale1=_addr(norm[0]),
+        d_shift1=_addr(norm[1]), d_scale2=_addr(norm[2]), d_shift2=_addr(norm[3]))
+    _native.check(_native.lib().octa_conv3x3_nhwc_wgrad(_native.ctx(x1.device.index), ctypes.byref(a), _native.current_stream_ptr()), "octa_conv3x3_nhwc_wgrad")
+    return None if into is not None else dw.view(3, 3, cout, cin).permute(2, 3, 0, 1)
+
+
 # ---- weight gradients on a side stream ---------------------------------------------------------------------------------
 # Weight gradients straight into `weight.grad` (round 5). A layer's weight gradient is a leaf of the backward graph: nothing reads it
 # before the optimiser step. Inside `direct_weight_grads()` (the trainers wrap `loss.backward()` in it, models/base_model_abc.py
 # backward_scope) the 3x3 weight-gradient launches write their result into the parameter's `.grad` in the parameter's own layout
-# (csrc/conv.hip octa_conv3x3_nhwc_wgrad_acc) -- ADDED to an existing gradient (a view of the data-parallel gradient arena, a second use
+# (csrc/conv.hip octa_conv3x3_nhwc_wgrad, out_mode OCTA_WGRAD_PARAM_ADD / _SET) -- ADDED to an existing gradient (a view of the data-parallel gradient arena, a second use
 # of the weight), written over a fresh buffer otherwise -- and the Function reports None to autograd: no [9][Cout][Cin] temporary, no
 # fill, no layout copy and no accumulation launch per layer (21 copies + 15 fills per U-Net step, ~3 per convolution of the GAN's
 # generator). Outside the context (tests, torch.autograd.grad, user code calling
@@ -33,7 +73,6 @@ USE_DIRECT_WGRAD = True         # module switch (tests / tools may clear it): ev
 # process-wide -- and hence one backward scope at a time: a second thread entering while one is open is refused (its backward would get
 # None for its weight gradients and find them written into .grad), torch.autograd.grad / .backward() outside a scope are unaffected
 _WG_ACTIVE = {"on": False, "owner": None}
-_WGRAD_TR = 2                   # the C side runs the transposing-read kernels at stride 1 and 2 (csrc/conv.hip use_tr): only they write into .grad
 DIRECT_WGRAD_COUNTS = [0, 0]    # weight gradients accumulated in place / returned to autograd
 
 
@@ -81,12 +120,7 @@ def _wgrad_to(weight, fn, into=None):
 
 def _wgrad_acc(x1, x2, dy, grad, accumulate, stride=1, tap_mask=0x1ff):
     """grad [Cout][Cin][3][3] float32 (+)= weight gradient of the 3x3 layer with input x1 (| x2 on the channel axis) and output gradient dy."""
-    n, h, w, c1 = x1.shape
-    cin = c1 + (x2.shape[3] if x2 is not None else 0)
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    rc = _native.lib().octa_conv3x3_nhwc_wgrad_acc(_native.ctx(x1.device.index), p(x1), p(x2), c1, p(dy), p(grad), n, h, w, cin, dy.shape[3], int(stride),
-                                                   int(tap_mask), int(accumulate), _native.current_stream_ptr())
-    _native.check(rc, "octa_conv3x3_nhwc_wgrad_acc")
+    _conv3x3_wgrad(x1, dy, x2, into=grad, accumulate=accumulate, stride=stride, tap_mask=tap_mask)
 
 
 USE_PACK_PLAN = True
@@ -240,26 +274,17 @@ def pack_convt2x2(w):
 def conv3x3_nhwc(x, wt, stride=1, in_dilation=1, tap_mask=0x1ff, residual=None):
     """x [N,H,W,Cin] bf16, wt [9,Cout,Cin] bf16 -> [N,Ho,Wo,Cout] bf16 (padding 1). tap_mask bit 3r+s = evaluate tap
     (r, s) of wt (as packed); cleared taps must have zero weights. residual (shape of the result, bf16) is added in the
-    kernel's epilogue (octa_conv3x3_nhwc_fwd6)."""
+    kernel's epilogue."""
     assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 4
     assert wt.dtype == torch.bfloat16 and wt.is_contiguous() and wt.shape[0] == 9 and wt.shape[2] == x.shape[3]
-    n, h, w, cin = x.shape
+    n, h, w, _ = x.shape
     cout = wt.shape[1]
     ho = (h * in_dilation - 1) // stride + 1
     wo = (w * in_dilation - 1) // stride + 1
     y = torch.empty((n, ho, wo, cout), dtype=torch.bfloat16, device=x.device)
     if residual is not None:
         assert residual.shape == y.shape and residual.dtype == torch.bfloat16 and residual.is_contiguous()
-        rc = _native.lib().octa_conv3x3_nhwc_fwd6(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), None, cin,
-                                                  ctypes.c_void_p(wt.data_ptr()), ctypes.c_void_p(y.data_ptr()), None, cout, n, h, w, cin, cout,
-                                                  int(stride), int(in_dilation), int(tap_mask), 1, 0, 0, None, None, None, None, 0.0, None,
-                                                  ctypes.c_void_p(residual.data_ptr()), _native.current_stream_ptr())
-        _native.check(rc, "octa_conv3x3_nhwc_fwd6")
-        return y
-    rc = _native.lib().octa_conv3x3_nhwc_fwd2(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), None, cin,
-                                              ctypes.c_void_p(wt.data_ptr()), ctypes.c_void_p(y.data_ptr()), None, cout, n, h, w, cin, cout,
-                                              int(stride), int(in_dilation), int(tap_mask), _native.current_stream_ptr())
-    _native.check(rc, "octa_conv3x3_nhwc_fwd2")
+    _conv3x3_fwd(x, wt, y, stride=stride, in_dilation=in_dilation, tap_mask=tap_mask, residual=residual)
     return y
 
 
@@ -287,15 +312,8 @@ def conv3x3_nhwc_wgrad(x, dy, tap_mask=0x1ff):
     """x [N,H,W,Cin] bf16, dy [N,H,W,Cout] bf16 (stride-1 layer) -> dW as a torch conv weight gradient
     [Cout, Cin, 3, 3] float32 (taps cleared in tap_mask come back as zero)."""
     assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and dy.dtype == torch.bfloat16 and dy.is_contiguous()
-    n, h, w, cin = x.shape
     assert dy.shape[:3] == x.shape[:3]
-    cout = dy.shape[3]
-    dw = torch.empty((9, cout, cin), dtype=torch.float32, device=x.device)
-    rc = _native.lib().octa_conv3x3_nhwc_wgrad2(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), None, cin,
-                                                ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(dw.data_ptr()), n, h, w, cin, cout, int(tap_mask),
-                                                _native.current_stream_ptr())
-    _native.check(rc, "octa_conv3x3_nhwc_wgrad2")
-    return dw.view(3, 3, cout, cin).permute(2, 3, 0, 1)
+    return _conv3x3_wgrad(x, dy, tap_mask=tap_mask)
 
 
 STAT_SLOTS = 16      # slots the tiles of an image spread their statistics atomics over
@@ -324,29 +342,19 @@ def _stat_slots(device, n, cout):
 
 def _conv_fwd_stats(x1, x2, wt, stride, want_stats):
     """Forward launch over one or two inputs (virtual concatenation); optionally also the InstanceNorm statistics of the result,
-    accumulated in the kernel's epilogue: want_stats = True / "slots" -> double [STAT_SLOTS][N][Cout][2] (round 5: octa_conv3x3_nhwc_fwd7),
-    "tiles" -> the round-1 per-tile partials float32 [N][tiles][Cout][2] (octa_conv3x3_nhwc_fwd5; kept for its tests)."""
-    n, h, w, c1 = x1.shape
-    c2 = x2.shape[3] if x2 is not None else 0
+    accumulated in the kernel's epilogue: want_stats = True / "slots" -> double [STAT_SLOTS][N][Cout][2], "tiles" -> the per-tile partials
+    float32 [N][tiles][Cout][2] (kept for their tests)."""
+    n, h, w, _ = x1.shape
     cout = wt.shape[1]
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
     y = torch.empty((n, ho, wo, cout), dtype=torch.bfloat16, device=x1.device)
-    part = None
-    if want_stats and want_stats != "tiles":
-        part = _stat_slots(x1.device, n, cout)
-        pp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        rc = _native.lib().octa_conv3x3_nhwc_fwd7(_native.ctx(x1.device.index), pp(x1), pp(x2), c1, pp(wt), pp(y), n, h, w, c1 + c2, cout, int(stride),
-                                                  pp(part), STAT_SLOTS, _native.current_stream_ptr())
-        _native.check(rc, "octa_conv3x3_nhwc_fwd7")
-        return y, part
-    if want_stats:
-        tiles = _native.lib().octa_conv_stat_tiles(ho, wo)
-        part = torch.empty((n, tiles, cout, 2), dtype=torch.float32, device=x1.device)
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    rc = _native.lib().octa_conv3x3_nhwc_fwd5(_native.ctx(x1.device.index), p(x1), p(x2), c1, p(wt), p(y), None, cout, n, h, w, c1 + c2, cout,
-                                              int(stride), 1, 0x1ff, 1, 0, 0, None, None, None, None, 0.0, p(part), _native.current_stream_ptr())
-    _native.check(rc, "octa_conv3x3_nhwc_fwd5")
-    return y, part
+    slots = tiles = None
+    if want_stats == "tiles":
+        tiles = torch.empty((n, _native.lib().octa_conv_stat_tiles(ho, wo), cout, 2), dtype=torch.float32, device=x1.device)
+    elif want_stats:
+        slots = _stat_slots(x1.device, n, cout)
+    _conv3x3_fwd(x1, wt, y, x2=x2, stride=stride, stat_partials=tiles, stat_slots=slots)
+    return y, (slots if slots is not None else tiles)
 
 
 # ---- zero-insertion-free stride-2 data gradient / 2x2 transposed convolution: one scattered launch per parity class
@@ -377,12 +385,8 @@ def _parity_table(device):
     return _parity_tables[key]
 
 
-def _fwd3(x, wt, y, cin, cout, mask, a, b):
-    n, h, w, _ = x.shape
-    rc = _native.lib().octa_conv3x3_nhwc_fwd3(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), None, cin, ctypes.c_void_p(wt.data_ptr()),
-                                              ctypes.c_void_p(y.data_ptr()), None, cout, n, h, w, cin, cout, 1, 1, int(mask), 2, int(a), int(b),
-                                              _native.current_stream_ptr())
-    _native.check(rc, "octa_conv3x3_nhwc_fwd3")
+def _fwd3(x, wt, y, mask, a, b):
+    _conv3x3_fwd(x, wt, y, tap_mask=mask, scatter=(2, a, b))
 
 
 def conv3x3_s2_dgrad(dy, weight):
@@ -395,7 +399,7 @@ def conv3x3_s2_dgrad(dy, weight):
     wp = (w9[src] * valid[:, :, None, None]).contiguous()                              # [4][9][ci][co]
     dx = torch.empty((n, 2 * ho, 2 * wo, cin), dtype=torch.bfloat16, device=dy.device)
     for p in range(4):
-        _fwd3(dy, slice_major(wp[p]), dx, cout, cin, masks[p], p >> 1, p & 1)
+        _fwd3(dy, slice_major(wp[p]), dx, masks[p], p >> 1, p & 1)
     return dx
 
 
@@ -407,7 +411,7 @@ def conv_transpose_2x2_fwd(x, weight):
     wp[:, 4] = weight.to(torch.bfloat16).permute(2, 3, 1, 0).reshape(4, cout, cin)
     y = torch.empty((n, 2 * h, 2 * w, cout), dtype=torch.bfloat16, device=x.device)
     for p in range(4):
-        _fwd3(x, slice_major(wp[p]), y, cin, cout, 1 << 4, p >> 1, p & 1)
+        _fwd3(x, slice_major(wp[p]), y, 1 << 4, p >> 1, p & 1)
     return y
 
 
@@ -430,8 +434,7 @@ def _pad_channels(x, mult=32):
     return out
 
 
-# A/B switch (development aid). The residual epilogue exists in the DMA-staged kernel only: with OCTA_CONV_GLDS=0 (the
-# register-staged kernel) the mailbox is never armed and autograd adds the two skip gradients itself.
+# A/B switch (development aid): cleared, the mailbox is never armed and autograd adds the two skip gradients itself.
 USE_SKIP_GRAD_FUSION = True
 
 
@@ -502,7 +505,7 @@ class _Conv3x3NHWC(torch.autograd.Function):
         elif ctx.mailbox is not None and ctx.mailbox.pending is not None:
             raise RuntimeError("skip gradient posted but the encoder convolution computes no input gradient")
         if ctx.needs_input_grad[1]:
-            direct = (lambda g, acc: _wgrad_acc(xp, None, dy, g, acc, st)) if (xp.shape[-1] == cin and _WGRAD_TR >= st and (st == 1 or (xp.shape[1] % 2 == 0 and xp.shape[2] % 2 == 0))) else None
+            direct = (lambda g, acc: _wgrad_acc(xp, None, dy, g, acc, st)) if (xp.shape[-1] == cin and (st == 1 or (xp.shape[1] % 2 == 0 and xp.shape[2] % 2 == 0))) else None
             if st == 1:
                 dw = _wgrad_to(weight, lambda: conv3x3_nhwc_wgrad(xp, dy)[:, :cin].to(weight.dtype), direct)
             else:
@@ -524,11 +527,9 @@ class _Conv3x3ReflectNHWC(torch.autograd.Function):
         y = torch.empty((n, h, w, cout), dtype=torch.bfloat16, device=x.device)
         wt = pack_weight(weight, cin)
         part = _stat_slots(x.device, n, cout) if want_stats else None       # InstanceNorm statistics from the epilogue (slot form, as conv3x3)
-        rc = _native.lib().octa_conv3x3_nhwc_fwd_pad_s(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(wt.data_ptr()),
-                                                       ctypes.c_void_p(y.data_ptr()), n, h, w, cin, cout, 1, 1,
-                                                       ctypes.c_void_p(part.data_ptr()) if part is not None else None, STAT_SLOTS if part is not None else 0,
-                                                       _native.current_stream_ptr())
-        _native.check(rc, "octa_conv3x3_nhwc_fwd_pad_s")
+        rc = _native.lib().octa_conv3x3_nhwc_fwd_pad(_native.ctx(x.device.index), _p(x), _p(wt), _p(y), n, h, w, cin, cout, 1, 1, _p(part),
+                                                     STAT_SLOTS if part is not None else 0, _native.current_stream_ptr())
+        _native.check(rc, "octa_conv3x3_nhwc_fwd_pad")
         ctx.save_for_backward(x, weight)
         if want_stats:
             ctx.mark_non_differentiable(part)
@@ -551,23 +552,22 @@ class _Conv3x3ReflectNHWC(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             wd = pack_weight_dgrad(weight, cin)
             dxp = torch.empty((n, h + 2, w + 2, cin), dtype=torch.bfloat16, device=x.device)
-            rc = lib.octa_conv3x3_nhwc_fwd_pad(hctx, ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(wd.data_ptr()), ctypes.c_void_p(dxp.data_ptr()),
-                                               n, h, w, cout, cin, 2, 0, _native.current_stream_ptr())
+            rc = lib.octa_conv3x3_nhwc_fwd_pad(hctx, _p(dy), _p(wd), _p(dxp), n, h, w, cout, cin, 2, 0, None, 0, _native.current_stream_ptr())
             _native.check(rc, "octa_conv3x3_nhwc_fwd_pad")
             dx = torch.empty_like(x)
             resample._launch("octa_reflect_pad_bwd", dxp, dx, n, h, w, cin, 1)
         if ctx.needs_input_grad[1]:
+            def wgrad_pad(d_dw, out_mode):
+                rc = lib.octa_conv3x3_nhwc_wgrad_pad(_native.ctx(x.device.index), _p(x), _p(dy), _p(d_dw), n, h, w, cin, cout, 1, 1, out_mode,
+                                                     _native.current_stream_ptr())
+                _native.check(rc, "octa_conv3x3_nhwc_wgrad_pad")
+
             def wg():
                 dwf = torch.empty((9, cout, cin), dtype=torch.float32, device=x.device)
-                rc = lib.octa_conv3x3_nhwc_wgrad_pad(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(dy.data_ptr()),
-                                                     ctypes.c_void_p(dwf.data_ptr()), n, h, w, cin, cout, 1, 1, _native.current_stream_ptr())
-                _native.check(rc, "octa_conv3x3_nhwc_wgrad_pad")
+                wgrad_pad(dwf, _native.WGRAD_TAP_MAJOR)
                 return dwf.view(3, 3, cout, cin).permute(2, 3, 0, 1).to(weight.dtype)
 
-            def direct(g, acc):
-                rc = lib.octa_conv3x3_nhwc_wgrad_pad_acc(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(dy.data_ptr()),
-                                                         ctypes.c_void_p(g.data_ptr()), n, h, w, cin, cout, 1, 1, int(acc), _native.current_stream_ptr())
-                _native.check(rc, "octa_conv3x3_nhwc_wgrad_pad_acc")
+            direct = lambda g, acc: wgrad_pad(g, _native.WGRAD_PARAM_ADD if acc else _native.WGRAD_PARAM_SET)
             dw = _wgrad_to(weight, wg, direct)
         return dx, dw, None
 
@@ -604,11 +604,9 @@ class _Conv3x3C1(torch.autograd.Function):
         wf = weight.reshape(cout, 9).float().contiguous()
         y = torch.empty((n, h, w, cout), dtype=torch.bfloat16, device=x.device)
         part = _stat_slots(x.device, n, cout) if want_stats else None
-        rc = _native.lib().octa_conv3x3_c1_fwd2(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(wf.data_ptr()),
-                                                ctypes.c_void_p(y.data_ptr()), n, h, w, cout,
-                                                ctypes.c_void_p(part.data_ptr()) if part is not None else None, STAT_SLOTS if part is not None else 0,
-                                                _native.current_stream_ptr())
-        _native.check(rc, "octa_conv3x3_c1_fwd2")
+        rc = _native.lib().octa_conv3x3_c1_fwd(_native.ctx(x.device.index), _p(x), _p(wf), _p(y), n, h, w, cout, _p(part),
+                                               STAT_SLOTS if part is not None else 0, _native.current_stream_ptr())
+        _native.check(rc, "octa_conv3x3_c1_fwd")
         ctx.save_for_backward(x)
         ctx.w_shape, ctx.w_dtype = weight.shape, weight.dtype
         ctx.weight_ref = weight
@@ -654,10 +652,6 @@ def conv3x3(x, weight, stride=1, want_stats=False, mailbox=None):
     return _Conv3x3NHWC.apply(x, weight, stride, want_stats, mailbox)
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class _Conv3x3CatNHWC(torch.autograd.Function):
     """y = conv3x3(cat(x1, x2, channel axis), weight), stride 1, without materialising the concatenation: the
     kernels read the two tensors as one virtual input and the data gradient is written straight into two tensors
@@ -685,23 +679,12 @@ class _Conv3x3CatNHWC(torch.autograd.Function):
         dy = dy.contiguous()
         if dy.dtype != torch.bfloat16:
             dy = dy.to(torch.bfloat16)
-        n, h, w, c1 = x1.shape
-        c2, cout = x2.shape[3], weight.shape[0]
-        lib, hctx, st = _native.lib(), _native.ctx(x1.device.index), _native.current_stream_ptr()
         dx1 = dx2 = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             dx1, dx2 = torch.empty_like(x1), torch.empty_like(x2)
-            wd = pack_weight_dgrad(weight)
-            rc = lib.octa_conv3x3_nhwc_fwd2(hctx, _p(dy), None, cout, _p(wd), _p(dx1), _p(dx2), c1, n, h, w, cout, c1 + c2, 1, 1, 0x1ff, st)
-            _native.check(rc, "octa_conv3x3_nhwc_fwd2 (data gradient)")
+            _conv3x3_fwd(dy, pack_weight_dgrad(weight), dx1, y2=dx2, what="octa_conv3x3_nhwc_fwd (data gradient)")
         if ctx.needs_input_grad[2]:
-            def wg():
-                dwf = torch.empty((9, cout, c1 + c2), dtype=torch.float32, device=x1.device)
-                rc = lib.octa_conv3x3_nhwc_wgrad2(_native.ctx(x1.device.index), _p(x1), _p(x2), c1, _p(dy), _p(dwf), n, h, w, c1 + c2, cout, 0x1ff,
-                                                  _native.current_stream_ptr())
-                _native.check(rc, "octa_conv3x3_nhwc_wgrad2")
-                return dwf.view(3, 3, cout, c1 + c2).permute(2, 3, 0, 1).to(weight.dtype)
-            dw = _wgrad_to(weight, wg, (lambda g, acc: _wgrad_acc(x1, x2, dy, g, acc)) if _WGRAD_TR >= 1 else None)
+            dw = _wgrad_to(weight, lambda: _conv3x3_wgrad(x1, dy, x2).to(weight.dtype), lambda g, acc: _wgrad_acc(x1, x2, dy, g, acc))
         if ctx.mailbox is not None and dx2 is not None and ctx.needs_input_grad[1]:
             assert ctx.mailbox.pending is None
             ctx.mailbox.pending, dx2 = dx2, None          # collected by the encoder convolution's data-gradient epilogue
@@ -724,18 +707,11 @@ class _InstNormLReLUNHWC(torch.autograd.Function):
         rstd = torch.empty_like(mean)
         w = weight.float().contiguous() if weight is not None else None
         b = bias.float().contiguous() if bias is not None else None
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        if partials is not None and partials.dtype == torch.float64:       # slot form (octa_conv3x3_nhwc_fwd7)
-            rc = _native.lib().octa_instnorm_lrelu_nhwc_fwd_s(_native.ctx(x.device.index), p(x), p(y), p(w), p(b), p(mean), p(rstd), B, C, hw,
-                                                              float(slope), float(eps), p(partials), int(partials.shape[0]),
-                                                              _native.current_stream_ptr())
-        elif partials is not None:
-            rc = _native.lib().octa_instnorm_lrelu_nhwc_fwd_p(_native.ctx(x.device.index), p(x), p(y), p(w), p(b), p(mean), p(rstd), B, C, hw,
-                                                              float(slope), float(eps), p(partials), int(partials.shape[1]),
-                                                              _native.current_stream_ptr())
-        else:
-            rc = _native.lib().octa_instnorm_lrelu_nhwc_fwd(_native.ctx(x.device.index), p(x), p(y), p(w), p(b), p(mean), p(rstd), B, C, hw,
-                                                            float(slope), float(eps), _native.current_stream_ptr())
+        slots = partials if partials is not None and partials.dtype == torch.float64 else None      # slot form; float32: per-tile partials
+        tiles = partials if slots is None else None
+        rc = _native.lib().octa_instnorm_lrelu_nhwc_fwd(_native.ctx(x.device.index), _p(x), _p(y), _p(w), _p(b), _p(mean), _p(rstd), B, C, hw, float(slope),
+                                                        float(eps), _p(tiles), int(tiles.shape[1]) if tiles is not None else 0, _p(slots),
+                                                        int(slots.shape[0]) if slots is not None else 0, _native.current_stream_ptr())
         _native.check(rc, "octa_instnorm_lrelu_nhwc_fwd")
         ctx.save_for_backward(x, w, b, mean, rstd)
         ctx.slope, ctx.has_w, ctx.has_b = float(slope), weight is not None, bias is not None
@@ -773,18 +749,11 @@ def _s2_wgrad(x_big, dy_small, taps2=((0, 1, 2), (0, 1, 2))):
     """Weight gradient [Cout, Cin, 3, 3] (float32) of a stride-2, padding-1 3x3 conv with input x_big [N,2H,2W,Cin] and
     output gradient dy_small [N,H,W,Cout]; taps2 = the (r, s) taps that are wanted (others come back zero)."""
     x_big, dy_small = x_big.contiguous(), dy_small.contiguous()
-    n, h, w, cin = x_big.shape
-    cout = dy_small.shape[-1]
     mask = 0
     for r in taps2[0]:
         for s_ in taps2[1]:
             mask |= 1 << (3 * r + s_)
-    dw = torch.empty((9, cout, cin), dtype=torch.float32, device=x_big.device)
-    rc = _native.lib().octa_conv3x3_nhwc_wgrad4(_native.ctx(x_big.device.index), ctypes.c_void_p(x_big.data_ptr()), None, cin,
-                                                ctypes.c_void_p(dy_small.data_ptr()), ctypes.c_void_p(dw.data_ptr()), n, h, w, cin, cout, 2, mask,
-                                                None, None, None, None, 0.0, _native.current_stream_ptr())
-    _native.check(rc, "octa_conv3x3_nhwc_wgrad4")
-    return dw.view(3, 3, cout, cin).permute(2, 3, 0, 1)
+    return _conv3x3_wgrad(x_big, dy_small, stride=2, tap_mask=mask)
 
 
 class _ConvT2x2NHWC(torch.autograd.Function):
@@ -913,11 +882,9 @@ class _Head1NHWC(torch.autograd.Function):
         n, h, w, c = x.shape
         wv = weight.reshape(-1).float().contiguous()
         y = torch.empty((n, h, w, 1), dtype=torch.bfloat16, device=x.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
         bv = bias.float().contiguous() if bias is not None else None      # read on the device: no host round trip in the step
-        rc = _native.lib().octa_head1_nhwc_fwd_b(_native.ctx(x.device.index), p(x), p(wv), p(bv) if bv is not None else None,
-                                                 n * h * w, c, p(y), _native.current_stream_ptr())
-        _native.check(rc, "octa_head1_nhwc_fwd_b")
+        rc = _native.lib().octa_head1_nhwc_fwd(_native.ctx(x.device.index), _p(x), _p(wv), _p(bv), n * h * w, c, _p(y), _native.current_stream_ptr())
+        _native.check(rc, "octa_head1_nhwc_fwd")
         ctx.save_for_backward(x, wv)
         ctx.w_shape, ctx.w_dtype, ctx.has_bias = weight.shape, weight.dtype, bias is not None
         return y
@@ -953,13 +920,10 @@ class _InstNormLReLUHead1NHWC(torch.autograd.Function):
         hb = head_b.float().contiguous() if head_b is not None else None
         mean, rstd = torch.empty(B * C, **f32), torch.empty(B * C, **f32)
         logits = torch.empty((B, H, W, 1), dtype=torch.bfloat16, device=x.device)
-        if partials is not None and partials.dtype == torch.float64:       # statistics of x in slot form from the convolution that wrote it
-            rc = _native.lib().octa_instnorm_lrelu_head1_nhwc_fwd_s(_native.ctx(x.device.index), _p(x), _p(g), _p(bt), _p(hw_), _p(hb), _p(mean), _p(rstd),
-                                                                    _p(logits), B, C, H * W, float(slope), float(eps), _p(partials),
-                                                                    int(partials.shape[0]), _native.current_stream_ptr())
-        else:
-            rc = _native.lib().octa_instnorm_lrelu_head1_nhwc_fwd(_native.ctx(x.device.index), _p(x), _p(g), _p(bt), _p(hw_), _p(hb), _p(mean), _p(rstd),
-                                                                  _p(logits), B, C, H * W, float(slope), float(eps), _native.current_stream_ptr())
+        slots = partials if partials is not None and partials.dtype == torch.float64 else None      # statistics of x from the convolution that wrote it
+        rc = _native.lib().octa_instnorm_lrelu_head1_nhwc_fwd(_native.ctx(x.device.index), _p(x), _p(g), _p(bt), _p(hw_), _p(hb), _p(mean), _p(rstd),
+                                                              _p(logits), B, C, H * W, float(slope), float(eps), _p(slots),
+                                                              int(slots.shape[0]) if slots is not None else 0, _native.current_stream_ptr())
         _native.check(rc, "octa_instnorm_lrelu_head1_nhwc_fwd")
         ctx.save_for_backward(x, g, bt, hw_, mean, rstd)
         ctx.slope = float(slope)
@@ -1091,11 +1055,7 @@ class _ConvLazy(torch.autograd.Function):
         assert weight.shape[1] == cin and c1 % 32 == 0 and c2 % 32 == 0 and cout % 32 == 0
         ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
         y = torch.empty((n, ho, wo, cout), dtype=torch.bfloat16, device=x1.device)
-        wt = pack_weight(weight)
-        rc = _native.lib().octa_conv3x3_nhwc_fwd4(_native.ctx(x1.device.index), _p(x1), _p(x2), c1, _p(wt), _p(y), None, cout, n, h, w, cin, cout,
-                                                  int(stride), 1, 0x1ff, 1, 0, 0, _p(sc1), _p(sh1), _p(sc2), _p(sh2), float(slope),
-                                                  _native.current_stream_ptr())
-        _native.check(rc, "octa_conv3x3_nhwc_fwd4")
+        _conv3x3_fwd(x1, pack_weight(weight), y, x2=x2, stride=stride, norm=(sc1, sh1, sc2, sh2), slope=slope)
         ctx.save_for_backward(x1, sc1, sh1, x2, sc2, sh2, weight)
         ctx.stride, ctx.slope = int(stride), float(slope)
         return y
@@ -1106,25 +1066,15 @@ class _ConvLazy(torch.autograd.Function):
         dy = dy.contiguous()
         if dy.dtype != torch.bfloat16:
             dy = dy.to(torch.bfloat16)
-        n, h, w, c1 = x1.shape
-        c2 = x2.shape[3] if x2 is not None else 0
-        cin, cout, st = c1 + c2, weight.shape[0], ctx.stride
-        lib, hctx, stream = _native.lib(), _native.ctx(x1.device.index), _native.current_stream_ptr()
+        st = ctx.stride
         dx1 = dx2 = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[3]:
             dx1 = torch.empty_like(x1)
             dx2 = torch.empty_like(x2) if x2 is not None else None
-            wd = pack_weight_dgrad(weight)
-            rc = lib.octa_conv3x3_nhwc_fwd4(hctx, _p(dy), None, cout, _p(wd), _p(dx1), _p(dx2), c1, n, dy.shape[1], dy.shape[2], cout, cin, 1, st,
-                                            0x1ff, 1, 0, 0, None, None, None, None, 0.0, stream)
-            _native.check(rc, "octa_conv3x3_nhwc_fwd4 (data gradient)")
+            _conv3x3_fwd(dy, pack_weight_dgrad(weight), dx1, y2=dx2, in_dilation=st, what="octa_conv3x3_nhwc_fwd (data gradient)")
         if ctx.needs_input_grad[6]:
             if st == 1:
-                dwf = torch.empty((9, cout, cin), dtype=torch.float32, device=x1.device)
-                rc = lib.octa_conv3x3_nhwc_wgrad3(hctx, _p(x1), _p(x2), c1, _p(dy), _p(dwf), n, h, w, cin, cout, 0x1ff, _p(sc1), _p(sh1), _p(sc2),
-                                                  _p(sh2), ctx.slope, stream)
-                _native.check(rc, "octa_conv3x3_nhwc_wgrad3")
-                dw = dwf.view(3, 3, cout, cin).permute(2, 3, 0, 1).to(weight.dtype)
+                dw = _conv3x3_wgrad(x1, dy, x2, norm=(sc1, sh1, sc2, sh2), slope=ctx.slope).to(weight.dtype)
             else:
                 xm = x1 if sc1 is None else _Materialise.apply(x1, sc1, sh1, ctx.slope)   # parity planes need the tensor itself
                 dw = _s2_wgrad(xm, dy).to(weight.dtype)

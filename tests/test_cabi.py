@@ -24,7 +24,22 @@ def test_python_binding_covers_header(hip_lib_built):
     from octa_autosegmentation_amd import _native
     assert sorted(_native.SIGNATURES) == declared_symbols()
     l = _native.lib()
-    assert l.octa_abi_version() == 1
+    assert l.octa_abi_version() == 2
+
+
+def test_struct_entry_points_check_size_and_context(hip_lib_built):
+    """The ctypes mirrors have the library's struct sizes: a correctly sized, otherwise empty struct gets as far as the NULL-context check,
+    a struct_size off by four is refused by the size check in front of it. No GPU is touched."""
+    from octa_autosegmentation_amd import _native
+    l = _native.lib()
+    for name, cls in (("octa_conv3x3_nhwc_fwd", _native.Conv3x3Args), ("octa_conv3x3_nhwc_wgrad", _native.Conv3x3WgradArgs)):
+        args = cls(struct_size=ctypes.sizeof(cls))
+        assert getattr(l, name)(None, ctypes.byref(args), None) == -2
+        assert l.octa_last_error().decode() == f"{name}: null pointer"
+        args.struct_size += 4
+        assert getattr(l, name)(None, ctypes.byref(args), None) == -2
+        msg = l.octa_last_error().decode()
+        assert "struct_size" in msg and str(ctypes.sizeof(cls)) in msg and str(ctypes.sizeof(cls) + 4) in msg, msg
 
 
 def test_no_gpu_is_loud(hip_lib_built):

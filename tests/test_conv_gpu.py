@@ -477,7 +477,7 @@ def test_transposed_conv_1x1_weight_gradient_on_the_mfma_kernel(hip_lib_built, h
 
 @pytest.mark.parametrize("stride_of_layer", [1, 2])
 def test_residual_epilogue_equals_separate_bf16_addition(hip_lib_built, stride_of_layer):
-    """octa_conv3x3_nhwc_fwd6: result + residual in the epilogue is bit for bit conv -> bf16, then a bf16 tensor addition
+    """octa_conv3x3_nhwc_fwd with d_residual: result + residual in the epilogue is bit for bit conv -> bf16, then a bf16 tensor addition
     (the data gradient of a stride-1 / stride-2 layer is the dilation-1 / dilation-2 launch)."""
     import torch
     from octa_autosegmentation_amd.models import mfma_conv

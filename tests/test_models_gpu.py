@@ -397,7 +397,7 @@ def test_reference_configs_never_leave_the_hand_written_kernels(cfg_file):
 
 def test_weight_gradients_added_straight_to_the_gradient_arena(monkeypatch):
     """Round 5 (models/mfma_conv.py direct_weight_grads): inside the trainers' backward scope the 3x3 weight-gradient launches add their
-    result to `weight.grad` in the parameter layout (octa_conv3x3_nhwc_wgrad_acc) and report None to autograd -- same kernels, same
+    result to `weight.grad` in the parameter layout (octa_conv3x3_nhwc_wgrad, out_mode OCTA_WGRAD_PARAM_ADD) and report None to autograd -- same kernels, same
     operands: every parameter gradient equals the pass that hands autograd one tensor per layer up to the summation order of the
     partial tiles (1e-4 of the tensor's scale), a second backward accumulates in place, and the convolutions really took that route."""
     from octa_autosegmentation_amd.models import mfma_conv
