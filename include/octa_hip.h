@@ -409,6 +409,35 @@ int octa_resize_bilinear_bwd(octa_ctx *ctx, const float *d_dy, int B, int h, int
 int octa_flip_rot90_rotate(octa_ctx *ctx, const float *d_in, float *d_out, int B, int N, const float *d_angle, const int *d_rot_k,
                            const int *d_flip, float threshold, int use_threshold, void *stream);
 
+/* ---- the augmentation of Menten et al. (MICCAI 2022), the reference's comparison baseline (csrc/menten.hip) --------------------
+ * MentenAugmentationd (reference data/data_transforms.py:44-325) = BinomialVesselNoised -> AddVitreousFloater -> AddMotionArtifact on samples
+ * in HBM. The random numbers are numpy's, drawn on the host in the reference's order and passed in; all arithmetic is float64. Every entry
+ * point takes a leading batch count B (tensors [B][H][W], contiguous); work buffers are the caller's and must not alias inputs or outputs.
+ * octa_menten_vessel_noise: d_img float32 (img_dtype 0) or float64 (1); d_bernoulli uint8 = np.random.binomial(1, 0.1); d_quantum float64 =
+ *   np.random.uniform(0, 0.2); d_weights float64 [2 radius + 1] = scipy's normalised Gaussian taps, radius <= 512. The Bernoulli field is dilated
+ *   once by the 3x3 cross (zero border), multiplied by 0.7 once per m in 0..4 with sqrt((y - H/2)^2 + (x - W/2)^2) < r - 3m (float64 compare,
+ *   strict), blurred (separable, scipy's `reflect` boundary) and scaled; d_out = clip((img + that + quantum) / (1 + scaling / 1.5), 0, 1).
+ *   d_tmp: float64 [B][H][W] work.
+ * octa_menten_floater_mask: d_pts int32 [B][P][2] = the corner points (first, second array index) of each sample's random walk, d_npts int32 [B]
+ *   how many of the P are used, d_dilations int32 [B]. d_mask uint8 [B][N][N] = binary_dilation(lines, cross, iterations = dilations): the
+ *   segments are drawn as skimage.draw.line does (Bresenham, both end points, clipped to the image), then every pixel within L1 distance
+ *   `dilations` of a line pixel is set (two separable scans, not `dilations` stencil launches). d_dist: int32 [B][N][N] work. N <= 4096.
+ * octa_menten_floater: that mask, gaussian_filter(mask, sigma) with the given taps (`reflect`), d_out = d_img * (1 - blurred), float64 [B][N][N].
+ *   d_mask, d_dist as above (the mask is left in d_mask), d_tmp float64 [B][N][N] work.
+ * octa_menten_motion: d_out[b][R][j] = j < shift ? 0 : source[j - shift] with (source row, shift) = d_table int32 [B][H][2]; a source row s >= 0
+ *   is row s of d_in[b], s < 0 is row -s - 1 of d_white [n_white][W] (the whiteout rows, already in the tensor's dtype). elem_size 4 or 8 bytes;
+ *   unit_elems elements move per access (unit of 4, 8 or 16 bytes): W, every shift and the tensors' addresses must be multiples of it. A table
+ *   entry that points outside its array yields zeros. The host folds the cuts of one call (shear / stretch / buckle / whiteout) into the table. */
+int octa_menten_vessel_noise(octa_ctx *ctx, const void *d_img, int img_dtype, const unsigned char *d_bernoulli, const double *d_quantum,
+                             const double *d_weights, int radius, double scaling, double r, int B, int H, int W, double *d_tmp, double *d_out,
+                             void *stream);
+int octa_menten_floater_mask(octa_ctx *ctx, const int *d_pts, const int *d_npts, const int *d_dilations, int B, int P, int N,
+                             unsigned char *d_mask, int *d_dist, void *stream);
+int octa_menten_floater(octa_ctx *ctx, const double *d_img, const int *d_pts, const int *d_npts, const int *d_dilations, const double *d_weights,
+                        int radius, int B, int P, int N, unsigned char *d_mask, int *d_dist, double *d_tmp, double *d_out, void *stream);
+int octa_menten_motion(octa_ctx *ctx, const void *d_in, void *d_out, int elem_size, const int *d_table, const void *d_white, int n_white,
+                       int unit_elems, int B, int H, int W, void *stream);
+
 /* First layer of the U-Net (UnetBasicBlock.conv1 of the input block: ONE input channel -> Cout in {8, 16, 32, 64}, 3x3,
  * padding 1, stride 1): d_x [N][H][W] bf16, d_w float32 [Cout][9] (tap = 3r + s), d_y [N][H][W][Cout] bf16; the weight
  * gradient d_dw float32 [Cout][9] (overwritten). Streaming kernels: 9 multiply-adds per output are not matrix-core work.

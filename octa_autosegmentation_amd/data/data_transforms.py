@@ -5,7 +5,8 @@ transformed where they will be consumed instead of in CPU loader workers (SURVEY
 
 Two groups:
 * the reference's OWN transforms on the hot path -- LoadGraphAndFilterByRandomRadiusd (:358-387), ToGrayScaled (:389-400),
-  SpeckleBrightnesd (:25-42), AddRandomBackgroundNoised (:498-516), ImageToImageTranslationd (:327-356);
+  SpeckleBrightnesd (:25-42), AddRandomBackgroundNoised (:498-516), ImageToImageTranslationd (:327-356), and the comparison baseline
+  MentenAugmentationd with its parts BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact (:44-325);
 * the MONAI transforms those configs name (LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, RandFlipd, RandRotate90d,
   RandRotated, Rotate90d, Flipd, AsDiscreted, CastToTyped; post-processing: Activations, AsDiscrete, RemoveSmallObjects,
   CastToType), restated from MONAI's documented behaviour. MONAI is neither in the image nor under /root/reference:
@@ -258,6 +259,213 @@ class AddRandomBackgroundNoised(MapTransform):
                     data[key] = torch.maximum(img, noise * speckle)      # float64 product, as torch promotes in the reference
         if self.delete_background and "background" in data:
             del data["background"]
+        return data
+
+
+# ---- the augmentation of Menten et al. (MICCAI 2022): the reference's comparison baseline (:44-325) -----------------------------------
+# Draws and host restatement: data/menten.py; kernels: csrc/menten.hip through data/gpu_augment.py. CUDA tensors of the layouts the loader
+# produces (image [1, H, W]; for the motion step a label of exactly [1, 4H, 4W]) go through the kernels. CPU tensors and other layouts take
+# the host restatement (numpy + scipy.ndimage, bit-identical to the reference); a CUDA tensor that has to take it says so.
+
+class HostFallbackError(RuntimeError):
+    pass
+
+
+_HOST_FALLBACK_WARNED = set()
+
+
+def _host_fallback(where, why):
+    """A CUDA tensor is about to be copied to the host and back because its layout is outside the HIP kernels: warn ONCE per (place,
+    reason), raise under OCTA_STRICT=1 (the convention of models/networks.py `_vendor_fallback`)."""
+    import os
+    import warnings
+    msg = (f"{where}: this CUDA sample leaves the HIP kernels (csrc/menten.hip) for the host restatement (numpy / scipy, a copy down and up): "
+           f"{why}. Results stay correct, speed does not; OCTA_STRICT=1 turns this into an error.")
+    if os.environ.get("OCTA_STRICT", "0") == "1":
+        raise HostFallbackError(msg)
+    if (where, why) not in _HOST_FALLBACK_WARNED:
+        _HOST_FALLBACK_WARNED.add((where, why))
+        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+
+
+def _device_image(x):
+    """None when `x` is a CUDA image [1, H, W] in float32 / float64 (the kernels' layout), else the reason it is not."""
+    if x.dim() != 3 or x.shape[0] != 1:
+        return f"shape {tuple(x.shape)} is not [1, H, W]"
+    if x.dtype not in (torch.float32, torch.float64):
+        return f"dtype {x.dtype} is neither float32 nor float64"
+    return None
+
+
+def _through_host(x, fn):
+    """The reference's `img.squeeze().numpy()` -> fn -> `torch.tensor(img).view(img_shape)`, on a copy, back on x's device."""
+    out = fn(x.detach().cpu().squeeze().numpy().copy())
+    return torch.tensor(out).view(x.shape).to(x.device)
+
+
+class BinomialVesselNoised(MapTransform):
+    """Binomial + quantum noise of Menten et al. (reference :44-102): a Bernoulli(0.1) field dilated once by the 3x3 cross, attenuated by 0.7
+    per ring sqrt((i - H/2)^2 + (j - W/2)^2) < r - 3m (m = 0..4), blurred (scipy gaussian_filter, `reflect`), scaled, added with
+    uniform(0, 0.2) noise, divided by 1 + scaling / 1.5 and clipped. Output float64 in the input's shape."""
+
+    def __init__(self, keys, allow_missing_keys: bool = False, vessel_noise_scaling=0.5, vessel_noise_blur=1.0, r=48) -> None:
+        super().__init__(keys, allow_missing_keys)
+        self.vessel_noise_scaling = vessel_noise_scaling
+        self.vessel_noise_blur = vessel_noise_blur
+        self.r = r
+
+    def rng_streams(self, has_background=True):
+        return {"numpy"}
+
+    def __call__(self, data):
+        from . import menten
+        data = dict(data)
+        for key in self.keys:
+            if key in data or not self.allow_missing_keys:
+                img = data[key]
+                why = None
+                if img.is_cuda:
+                    why = _device_image(img)
+                    if why is None and not (0 < float(self.vessel_noise_blur) and menten.gaussian_radius(self.vessel_noise_blur) <= 512):
+                        why = f"vessel_noise_blur {self.vessel_noise_blur} is outside the kernel's radius range"
+                    if why is not None:
+                        _host_fallback("BinomialVesselNoised", why)
+                if img.is_cuda and why is None:
+                    from .gpu_augment import menten_vessel_noise
+                    bern, quantum = menten.vessel_noise_draws(tuple(img.shape[-2:]))
+                    dev = img.device
+                    data[key] = menten_vessel_noise(img, torch.from_numpy(bern).to(dev).unsqueeze(0), torch.from_numpy(quantum).to(dev).unsqueeze(0),
+                                                    self.vessel_noise_blur, self.vessel_noise_scaling, self.r)
+                else:
+                    data[key] = _through_host(img, lambda a: menten.vessel_noise_host(a, self.vessel_noise_scaling, self.vessel_noise_blur, self.r))
+        return data
+
+
+class AddVitreousFloater(MapTransform):
+    """Vitreous floater of Menten et al. (reference :104-185): with probability floater_chance a random walk of Bresenham segments, dilated
+    `dilations` times by the 3x3 cross and blurred with sigma 10, darkens the image: img * (1 - floater), float64. Without a floater the image
+    comes back unchanged in its own dtype. As in the reference, the drawn opacity has no effect (the dilation makes the mask boolean) and
+    the mask is allocated as (W, H), so a floater on a non-square image raises numpy's broadcasting ValueError -- after its draws."""
+
+    def __init__(self, keys, allow_missing_keys: bool = False, floater_chance: float = 0.1, floater_opacity_interval=(0.5, 1.0),
+                 floater_segments_interval=(10, 20), dilations_interval=(10, 30)) -> None:
+        super().__init__(keys, allow_missing_keys)
+        self.floater_chance = floater_chance
+        self.floater_opacity_interval = floater_opacity_interval
+        self.floater_segments_interval = floater_segments_interval
+        self.dilations_interval = dilations_interval
+
+    def rng_streams(self, has_background=True):
+        return {"numpy"}
+
+    def __call__(self, data):
+        from . import menten
+        data = dict(data)
+        for key in self.keys:
+            if key in data or not self.allow_missing_keys:
+                img = data[key]
+                if img.squeeze().dim() != 2:
+                    raise ValueError(f"AddVitreousFloater: {tuple(img.shape)} does not squeeze to a 2-D image")
+                H, W = img.squeeze().shape
+                draws = menten.floater_draws(H, W, self.floater_chance, self.floater_opacity_interval, self.floater_segments_interval,
+                                             self.dilations_interval)
+                if draws is None:
+                    data[key] = img.clone()
+                    continue
+                points, opacity, dilations = draws
+                why = None
+                if img.is_cuda:
+                    why = _device_image(img)
+                    if why is None and H != W:
+                        # the reference's `img * (1 - floater)` with floater of shape (W, H)
+                        raise ValueError(f"operands could not be broadcast together with shapes ({H},{W}) ({W},{H}) ")
+                    if why is None and (dilations < 1 or W > 4096):
+                        why = f"dilations {dilations} / size {W} outside the kernel's range"
+                    if why is not None:
+                        _host_fallback("AddVitreousFloater", why)
+                if img.is_cuda and why is None:
+                    from .gpu_augment import menten_floater
+                    segs = points if opacity != 0 else points[:1]           # an opacity of exactly 0 leaves the mask empty
+                    data[key] = menten_floater(img.double(), [segs], [dilations])
+                else:
+                    data[key] = _through_host(img, lambda a: menten.floater_host(a, draws))
+        return data
+
+
+class AddMotionArtifact(MapTransform):
+    """Motion artifacts of Menten et al. (reference :187-302): up to no_h_cuts - 1 horizontal cuts, each a shear (rows below shifted right,
+    zero filled), stretch (one row repeated), buckle (rows repeated from above) or whiteout (rows of uniform(0.5, 1) noise, image only) at a
+    random row; the label (four times the image's resolution) gets the same cut at 4 x position and 4 x amount. dtypes are kept; new tensors
+    are returned (the reference writes through `.numpy()` into its inputs). As in the reference, `__call__` does not hand `no_h_cuts` on to
+    `add_motion_artifact`, whose own default (3) therefore always applies."""
+
+    def __init__(self, img_key, gt_key, artifacts={'shear': 0.3, 'stretch': 0.3, 'buckle': 0.3, 'whiteout': 0.1}, grace_margin: int = 10,
+                 max_shear: int = 5, max_stretch: int = 5, max_buckle: int = 5, max_whiteout: int = 1, no_h_cuts: int = 3) -> None:
+        super().__init__([img_key, gt_key], False)
+        self.img_key = img_key
+        self.gt_key = gt_key
+        self.artifacts = artifacts
+        self.grace_margin = grace_margin
+        self.max_shear = max_shear
+        self.max_stretch = max_stretch
+        self.max_buckle = max_buckle
+        self.max_whiteout = max_whiteout
+        self.no_h_cuts = no_h_cuts
+
+    def rng_streams(self, has_background=True):
+        return {"numpy"}
+
+    def __call__(self, data):
+        from . import menten
+        data = dict(data)
+        img, gt = data[self.img_key], data[self.gt_key]
+        why = None
+        if img.is_cuda or gt.is_cuda:
+            ok = lambda t: t.is_cuda and t.dim() == 3 and t.shape[0] == 1 and t.is_floating_point() and t.element_size() in (4, 8)
+            if not (ok(img) and ok(gt)):
+                why = f"image {tuple(img.shape)} {img.dtype} on {img.device} / label {tuple(gt.shape)} {gt.dtype} on {gt.device} are not [1, H, W] CUDA tensors of 4- or 8-byte floats"
+            elif (gt.shape[1], gt.shape[2]) != (4 * img.shape[1], 4 * img.shape[2]):
+                why = f"label {tuple(gt.shape)} is not [1, 4H, 4W] of image {tuple(img.shape)}"
+            if why is not None:
+                _host_fallback("AddMotionArtifact", why)
+        h, w = img.squeeze().shape
+        cuts = menten.motion_draws(h, w, self.artifacts, self.grace_margin, self.max_shear, self.max_stretch, self.max_buckle, self.max_whiteout)
+        if img.is_cuda and gt.is_cuda and why is None:
+            from .gpu_augment import menten_motion
+            H, W = img.shape[1:]
+            table, white = menten.fold_cuts(H, W, cuts, 1)
+            data[self.img_key] = menten_motion(img, table, white)
+            data[self.gt_key] = menten_motion(gt, menten.fold_cuts(H, W, cuts, 4)[0])
+        else:
+            a, g = menten.motion_host(img.detach().cpu().squeeze().numpy().copy(), gt.detach().cpu().squeeze().numpy().copy(), cuts)
+            data[self.img_key] = torch.tensor(a).view(img.shape).to(img.device)
+            data[self.gt_key] = torch.tensor(g).view(gt.shape).to(gt.device)
+        return data
+
+
+class MentenAugmentationd(MapTransform):
+    """BinomialVesselNoised -> AddVitreousFloater -> AddMotionArtifact with their defaults (reference :304-325), the augmentation of
+
+    Physiology-Based Simulation of the Retinal Vasculature Enables Annotation-Free Segmentation of OCT Angiographs
+    M. J. Menten, J. C. Paetzold, A. Dima, B. H. Menze, B. Knier, D. Rueckert, MICCAI 2022
+
+    which the reference's paper compares its noise model against (configs/config_ves_seg-S_Menten_aug.yml)."""
+
+    def __init__(self, img_key: str, gt_key: str) -> None:
+        super().__init__(keys=[img_key, gt_key], allow_missing_keys=False)
+        self.img_key = img_key
+        self.gt_key = gt_key
+        self.binomialVesselNoised = BinomialVesselNoised([img_key], allow_missing_keys=True)
+        self.vitreousFloater = AddVitreousFloater([img_key], allow_missing_keys=True)
+        self.add_motion_artifact = AddMotionArtifact(img_key, gt_key)
+
+    def rng_streams(self, has_background=True):
+        return {"numpy"}
+
+    def __call__(self, data):
+        data = self.binomialVesselNoised(data)
+        data = self.vitreousFloater(data)
+        data = self.add_motion_artifact(data)
         return data
 
 
@@ -584,6 +792,7 @@ class CastToType:
 
 TRANSFORMS = {c.__name__: c for c in (
     LoadGraphAndFilterByRandomRadiusd, ToGrayScaled, SpeckleBrightnesd, AddRandomBackgroundNoised, ImageToImageTranslationd,
+    BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact, MentenAugmentationd,
     LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, Flipd, RandFlipd, Rotate90d, RandRotate90d, RandRotated, AsDiscreted,
     CastToTyped, Activations, AsDiscrete, RemoveSmallObjects, Resize, CastToType)}
 

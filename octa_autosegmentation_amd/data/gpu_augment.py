@@ -174,3 +174,101 @@ class GpuSegAugmentation:
             out[key] = flip_rot90_rotate(y, ang_t, k_t, flip_t, thr).unsqueeze(1)
         out["params"] = dict(flip=flip, rot_k=k, angle=ang)
         return out
+
+
+# ---- the Menten et al. augmentation (csrc/menten.hip; draws and host restatement: data/menten.py) ------------------------------------
+
+_MENTEN_WEIGHTS = {}
+
+
+def _gauss_weights(sigma, device):
+    """scipy's Gaussian taps for `sigma` as a float64 device tensor, computed on the host once per (sigma, device)."""
+    from . import menten
+    key = (float(sigma), str(device))
+    if key not in _MENTEN_WEIGHTS:
+        _MENTEN_WEIGHTS[key] = torch.from_numpy(menten.gaussian_weights(sigma)).to(device)
+    return _MENTEN_WEIGHTS[key]
+
+
+def menten_vessel_noise(img, bernoulli, quantum, sigma=1.0, scaling=0.5, r=48):
+    """BinomialVesselNoised on a device batch: img float32 / float64 [B,H,W], bernoulli uint8 [B,H,W] (np.random.binomial(1, 0.1)), quantum
+    float64 [B,H,W] (np.random.uniform(0, 0.2)). -> float64 [B,H,W]."""
+    assert img.is_cuda and img.dim() == 3 and img.dtype in (torch.float32, torch.float64)
+    assert bernoulli.shape == img.shape and bernoulli.dtype == torch.uint8 and quantum.shape == img.shape and quantum.dtype == torch.float64
+    img, bernoulli, quantum = img.contiguous(), bernoulli.contiguous(), quantum.contiguous()
+    w = _gauss_weights(sigma, img.device)
+    B, H, W = img.shape
+    tmp = torch.empty((B, H, W), dtype=torch.float64, device=img.device)
+    out = torch.empty_like(tmp)
+    rc = _native.lib().octa_menten_vessel_noise(_native.ctx(img.device.index), _p(img), 0 if img.dtype == torch.float32 else 1, _p(bernoulli), _p(quantum),
+                                                _p(w), (w.numel() - 1) // 2, float(scaling), float(r), B, H, W, _p(tmp), _p(out),
+                                                _native.current_stream_ptr())
+    _native.check(rc, "octa_menten_vessel_noise")
+    return out
+
+
+def _floater_args(points, dilations, device):
+    """[int array [n_b + 1, 2]] per sample, [int] -> device int32 tensors pts [B,P,2], npts [B], dil [B]."""
+    P = max(len(p) for p in points)
+    pts = np.zeros((len(points), P, 2), dtype=np.int32)
+    for b, p in enumerate(points):
+        pts[b, :len(p)] = np.asarray(p, dtype=np.int32).reshape(-1, 2)
+    npts = np.array([len(p) for p in points], dtype=np.int32)
+    dil = np.asarray(dilations, dtype=np.int32).reshape(len(points))
+    return tuple(torch.from_numpy(a).to(device) for a in (pts, npts, dil)) + (P,)
+
+
+def menten_floater_mask(points, dilations, N, device):
+    """The boolean mask of AddVitreousFloater alone, binary_dilation(lines, iterations=dilations), for B samples: points[b] int [n_b + 1, 2] (the
+    corners of the walk, indices along the mask's (first, second) axis), dilations[b] >= 1. -> bool [B,N,N] on `device`."""
+    pts, npts, dil, P = _floater_args(points, dilations, device)
+    B = pts.shape[0]
+    mask = torch.empty((B, N, N), dtype=torch.uint8, device=device)
+    dist = torch.empty((B, N, N), dtype=torch.int32, device=device)
+    rc = _native.lib().octa_menten_floater_mask(_native.ctx(mask.device.index), _p(pts), _p(npts), _p(dil), B, P, N, _p(mask), _p(dist),
+                                                _native.current_stream_ptr())
+    _native.check(rc, "octa_menten_floater_mask")
+    return mask.bool()
+
+
+def menten_floater(img, points, dilations, sigma=10):
+    """AddVitreousFloater on a device batch of SQUARE float64 images [B,N,N] that all get a floater: img * (1 - gaussian_filter(mask, sigma)) with
+    the mask of menten_floater_mask. -> float64 [B,N,N]."""
+    assert img.is_cuda and img.dim() == 3 and img.shape[1] == img.shape[2] and img.dtype == torch.float64 and len(points) == img.shape[0]
+    img = img.contiguous()
+    B, N, _ = img.shape
+    pts, npts, dil, P = _floater_args(points, dilations, img.device)
+    w = _gauss_weights(sigma, img.device)
+    mask = torch.empty((B, N, N), dtype=torch.uint8, device=img.device)
+    dist = torch.empty((B, N, N), dtype=torch.int32, device=img.device)
+    tmp = torch.empty_like(img)
+    out = torch.empty_like(img)
+    rc = _native.lib().octa_menten_floater(_native.ctx(img.device.index), _p(img), _p(pts), _p(npts), _p(dil), _p(w), (w.numel() - 1) // 2, B, P, N,
+                                           _p(mask), _p(dist), _p(tmp), _p(out), _native.current_stream_ptr())
+    _native.check(rc, "octa_menten_floater")
+    return out
+
+
+def menten_motion(x, table, white=None):
+    """AddMotionArtifact's cuts as one gather (data/menten.py fold_cuts): x [B,H,W] of a 4- or 8-byte dtype, table int32 numpy [B,H,2] or [H,2]
+    (source row, shift), white float64 numpy [k,W] (whiteout rows, cast to x's dtype as numpy's assignment does) or None. -> new tensor like x."""
+    assert x.is_cuda and x.dim() == 3 and x.element_size() in (4, 8)
+    x = x.contiguous()
+    B, H, W = x.shape
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.int32).reshape(B, H, 2))
+    esz = x.element_size()
+    unit = 16 // esz                                     # 16-byte accesses where the row length and every shift allow it
+    while unit > 1 and (W % unit or np.any(table[..., 1] % unit) or x.data_ptr() % (unit * esz)):
+        unit //= 2
+    d_white, n_white = None, 0
+    if white is not None:
+        np_dtype = torch.empty((), dtype=x.dtype).numpy().dtype
+        d_white = torch.from_numpy(np.ascontiguousarray(np.asarray(white).astype(np_dtype))).to(x.device)
+        n_white = d_white.shape[0]
+        assert d_white.shape[1] == W
+    d_table = torch.from_numpy(table).to(x.device)
+    out = torch.empty_like(x)
+    rc = _native.lib().octa_menten_motion(_native.ctx(x.device.index), _p(x), _p(out), esz, _p(d_table), _p(d_white), n_white, unit, B, H, W,
+                                          _native.current_stream_ptr())
+    _native.check(rc, "octa_menten_motion")
+    return out
