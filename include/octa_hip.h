@@ -438,6 +438,26 @@ int octa_menten_floater(octa_ctx *ctx, const double *d_img, const int *d_pts, co
 int octa_menten_motion(octa_ctx *ctx, const void *d_in, void *d_out, int elem_size, const int *d_table, const void *d_white, int n_white,
                        int unit_elems, int B, int H, int W, void *stream);
 
+/* ---- the reference's handcrafted noise model (csrc/noise_model.hip, csrc/philox.h) ------------------------------------------------
+ * NoiseModeld (reference data/data_transforms.py:435-475) -> models/noise_model.py:56-91 NoiseModel.forward(adversarial = False) at
+ * downsample_factor 1, for a mini-batch in ONE launch. d_img, d_background, d_out: float32 [B][H][W], contiguous; d_out aliases neither input.
+ * d_grids float32 [B][5][gh][gw]: the control points as the reference holds them -- alpha and beta of the vessel noise, alpha and beta of
+ *   the speckle noise (10^(2 x - 1), x ~ Beta(2, 2)), and the gamma grid (uniform(0, 1)). Each is upsampled as torch's bicubic interpolation
+ *   does (align_corners False, A = -0.75, tap indices clamped); the four alpha / beta maps are clamped to >= 1e-3, the gamma grid is first
+ *   mapped to clamp(g, 0, 1) 2 lambda_gamma + (1 - lambda_gamma). gh gw <= 1024.
+ * Per pixel Delta ~ Beta(alpha_v, beta_v), N ~ Beta(alpha_s, beta_s), drawn ON THE DEVICE: Philox-4x32-10 keyed by `seed`, countered by
+ *   (pixel y W + x, sample_offset + b, field, round). The same seed gives the same bits whatever B and the launch geometry are; sample b of a
+ *   batch equals a B = 1 call with sample_offset + b. The sampler (two Gamma variates in log space, Marsaglia-Tsang with at most 16 attempts
+ *   each) cannot loop on any input and returns finite values in [0, 1].
+ * d_out = pow(max(img, background lambda_delta Delta) (lambda_speckle N + 1 - lambda_speckle) + 1e-6, Gamma), float32 arithmetic in that order.
+ * Optional (NULL = absent): d_delta_in, d_n_in float32 [B][H][W] REPLACE the drawn field (each on its own); d_maps float32 [B][5][H][W]
+ *   receives the five maps the pixel arithmetic used (alpha / beta maps after the clamp, Gamma); d_fields float32 [B][2][H][W] Delta and N.
+ * octa_philox4x32_10: the generator itself on the HOST (counter4, key2, out4: host pointers), for known-answer tests. */
+int octa_noise_model(octa_ctx *ctx, const float *d_img, const float *d_background, const float *d_grids, int B, int H, int W, int gh, int gw,
+                     uint64_t seed, uint32_t sample_offset, double lambda_delta, double lambda_speckle, double lambda_gamma,
+                     const float *d_delta_in, const float *d_n_in, float *d_out, float *d_maps, float *d_fields, void *stream);
+void octa_philox4x32_10(const uint32_t *counter4, const uint32_t *key2, uint32_t *out4);
+
 /* First layer of the U-Net (UnetBasicBlock.conv1 of the input block: ONE input channel -> Cout in {8, 16, 32, 64}, 3x3,
  * padding 1, stride 1): d_x [N][H][W] bf16, d_w float32 [Cout][9] (tap = 3r + s), d_y [N][H][W][Cout] bf16; the weight
  * gradient d_dw float32 [Cout][9] (overwritten). Streaming kernels: 9 multiply-adds per output are not matrix-core work.

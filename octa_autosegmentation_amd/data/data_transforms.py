@@ -6,7 +6,8 @@ transformed where they will be consumed instead of in CPU loader workers (SURVEY
 Two groups:
 * the reference's OWN transforms on the hot path -- LoadGraphAndFilterByRandomRadiusd (:358-387), ToGrayScaled (:389-400),
   SpeckleBrightnesd (:25-42), AddRandomBackgroundNoised (:498-516), ImageToImageTranslationd (:327-356), and the comparison baseline
-  MentenAugmentationd with its parts BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact (:44-325);
+  MentenAugmentationd with its parts BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact (:44-325), and the paper's own noise
+  model NoiseModeld with RandomDecreaseResolutiond (:435-496);
 * the MONAI transforms those configs name (LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, RandFlipd, RandRotate90d,
   RandRotated, Rotate90d, Flipd, AsDiscreted, CastToTyped; post-processing: Activations, AsDiscrete, RemoveSmallObjects,
   CastToType), restated from MONAI's documented behaviour. MONAI is neither in the image nor under /root/reference:
@@ -274,12 +275,13 @@ class HostFallbackError(RuntimeError):
 _HOST_FALLBACK_WARNED = set()
 
 
-def _host_fallback(where, why):
+def _host_fallback(where, why, kernels="csrc/menten.hip", host="numpy / scipy"):
     """A CUDA tensor is about to be copied to the host and back because its layout is outside the HIP kernels: warn ONCE per (place,
-    reason), raise under OCTA_STRICT=1 (the convention of models/networks.py `_vendor_fallback`)."""
+    reason), raise under OCTA_STRICT=1 (the convention of models/networks.py `_vendor_fallback`). `kernels` / `host` name the source file
+    the sample leaves and what the host restatement runs on."""
     import os
     import warnings
-    msg = (f"{where}: this CUDA sample leaves the HIP kernels (csrc/menten.hip) for the host restatement (numpy / scipy, a copy down and up): "
+    msg = (f"{where}: this CUDA sample leaves the HIP kernels ({kernels}) for the host restatement ({host}, a copy down and up): "
            f"{why}. Results stay correct, speed does not; OCTA_STRICT=1 turns this into an error.")
     if os.environ.get("OCTA_STRICT", "0") == "1":
         raise HostFallbackError(msg)
@@ -466,6 +468,107 @@ class MentenAugmentationd(MapTransform):
         data = self.binomialVesselNoised(data)
         data = self.vitreousFloater(data)
         data = self.add_motion_artifact(data)
+        return data
+
+
+# ---- the reference's noise model: the "random augmentation" configuration (configs/config_ves_seg-S_RA.yml; reference :435-496) -------------
+# Draws and host restatement: data/noise_model.py; kernel: csrc/noise_model.hip through data/gpu_augment.py.
+
+class NoiseModeld(MapTransform):
+    """The paper's handcrafted noise model (reference :435-475 -> models/noise_model.py NoiseModel.forward, adversarial=False): background
+    vessels `max(I, I_d lambda_delta Delta)`, speckle `(lambda_speckle N + 1 - lambda_speckle)`, contrast `pow(. + 1e-6, Gamma)`, where Delta and
+    N are per-pixel Beta variates whose two shape maps, like Gamma, are bicubic upsamplings of random gh x gw control grids. The sample must
+    hold a `background` tensor of the image's shape; it stays in the sample. One `random.random() < prob` is drawn per call, at prob 1 too.
+    As in the reference, a key that is missing raises whatever allow_missing_keys says; `alpha` is the step size of the adversarial mode,
+    which is not part of this package, and is only kept.
+
+    CPU tensors take the host restatement (data/noise_model.py), bit-identical to the reference's class for the same torch.manual_seed.
+    CUDA float32 tensors [1, H, W] with downsample_factor 1 take csrc/noise_model.hip: the control grids are drawn on the host from torch's
+    global generator exactly as on the host path (the FIRST call of an instance draws them twice, as the reference does), then ONE 64-bit
+    seed is drawn from the same generator and the per-pixel Beta fields are made on the device by a counter-based generator keyed with it.
+    torch.manual_seed therefore fixes a run on either path, and both paths use the same control points -- but they leave torch's generator
+    at DIFFERENT positions: the host path consumes two H x W Beta fields from it per call, the device path one integer. Whatever draws from
+    torch's generator afterwards differs between a host and a device run; the per-pixel fields differ too (same distribution, other bits).
+    Any other CUDA layout takes the host restatement and says so (warning once; error under OCTA_STRICT=1)."""
+
+    def __init__(self, keys, prob=1, allow_missing_keys: bool = False, grid_size=(9, 9), lambda_delta=1, lambda_speckle=0.7, lambda_gamma=0.3,
+                 alpha=0.2, downsample_factor=1) -> None:
+        super().__init__(keys, allow_missing_keys)
+        from .noise_model import NoiseModelDraws
+        self.prob = prob
+        self.grid_size = tuple(grid_size)
+        self.lambda_delta, self.lambda_speckle, self.lambda_gamma = lambda_delta, lambda_speckle, lambda_gamma
+        self.alpha = alpha
+        self.downsample_factor = downsample_factor
+        self.draws = NoiseModelDraws(self.grid_size)
+
+    def rng_streams(self, has_background=True):
+        return {"python", "torch"}
+
+    def _why_not_device(self, img, background):
+        if img.dim() != 3 or img.shape[0] != 1:
+            return f"shape {tuple(img.shape)} is not [1, H, W]"
+        if self.downsample_factor != 1:
+            return f"downsample_factor {self.downsample_factor} is not 1"
+        if img.dtype != torch.float32 or background.dtype != torch.float32:
+            return f"dtypes {img.dtype} / {background.dtype} (background) are not float32"
+        if not background.is_cuda or background.shape != img.shape:
+            return f"background {tuple(background.shape)} on {background.device} does not match the image {tuple(img.shape)} on {img.device}"
+        return None
+
+    def __call__(self, data):
+        from . import noise_model as nm
+        data = dict(data)
+        if _py_random.random() < self.prob:
+            for key in self.keys:
+                img, background = data[key], data["background"]
+                why = None
+                if img.is_cuda:
+                    why = self._why_not_device(img, background)
+                    if why is not None:
+                        _host_fallback("NoiseModeld", why, kernels="csrc/noise_model.hip", host="torch on the CPU")
+                if img.is_cuda and why is None:
+                    from .gpu_augment import noise_model
+                    grids = torch.cat(self.draws.control_points(1, img.dtype), dim=1)           # [1, 5, gh, gw]
+                    seed = int(torch.empty((), dtype=torch.int64).random_().item())
+                    data[key] = noise_model(img, background, grids, seed, self.lambda_delta, self.lambda_speckle, self.lambda_gamma)
+                else:
+                    I, I_d = img.detach().cpu().unsqueeze(0), background.detach().cpu().unsqueeze(0)  # noqa: E741
+                    out = nm.noise_model_host(I, I_d, self.draws.control_points(1, I.dtype), self.lambda_delta, self.lambda_speckle,
+                                              self.lambda_gamma, self.downsample_factor)
+                    data[key] = out.squeeze(0).detach().to(img.device)
+        return data
+
+
+class RandomDecreaseResolutiond(MapTransform):
+    """Lower the resolution by a random factor and bring the image back to its size, both by nearest-neighbour resampling (reference :477-496):
+    `random.uniform(0, 1) < p`, then per key `factor = random.uniform(max_factor, 1)`, interpolate(scale_factor=factor), interpolate(size).
+    As in the reference, allow_missing_keys is set but a missing key raises. CPU tensors go through torch's two interpolations; on CUDA
+    tensors the two resamples are one gather per axis with index tables that torch's CPU nearest kernel itself produced
+    (data/noise_model.py nearest_roundtrip_tables), so the result is the CPU result exactly, not the device kernel's own rounding."""
+
+    def __init__(self, keys, p=1, max_factor=0.25) -> None:
+        super().__init__(keys, True)
+        self.max_factor = max_factor
+        self.p = p
+
+    def rng_streams(self, has_background=True):
+        return {"python"}
+
+    def __call__(self, data):
+        from .noise_model import nearest_roundtrip_tables
+        data = dict(data)
+        if _py_random.uniform(0, 1) < self.p:
+            for key in self.keys:
+                d = data[key]
+                factor = _py_random.uniform(self.max_factor, 1)
+                if d.is_cuda:
+                    for axis, table in enumerate(nearest_roundtrip_tables(d.shape[1:], factor)):
+                        d = d.index_select(axis + 1, table.to(d.device))
+                else:
+                    d = torch.nn.functional.interpolate(d.unsqueeze(0), scale_factor=factor)
+                    d = torch.nn.functional.interpolate(d, size=data[key].shape[1:]).squeeze(0)
+                data[key] = d
         return data
 
 
@@ -792,7 +895,7 @@ class CastToType:
 
 TRANSFORMS = {c.__name__: c for c in (
     LoadGraphAndFilterByRandomRadiusd, ToGrayScaled, SpeckleBrightnesd, AddRandomBackgroundNoised, ImageToImageTranslationd,
-    BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact, MentenAugmentationd,
+    BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact, MentenAugmentationd, NoiseModeld, RandomDecreaseResolutiond,
     LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, Flipd, RandFlipd, Rotate90d, RandRotate90d, RandRotated, AsDiscreted,
     CastToTyped, Activations, AsDiscrete, RemoveSmallObjects, Resize, CastToType)}
 

@@ -272,3 +272,29 @@ def menten_motion(x, table, white=None):
                                           _native.current_stream_ptr())
     _native.check(rc, "octa_menten_motion")
     return out
+
+
+# ---- the reference's noise model (csrc/noise_model.hip; control-point draws and host restatement: data/noise_model.py) --------------------------
+
+def noise_model(img, background, grids, seed, lambda_delta=1, lambda_speckle=0.7, lambda_gamma=0.3, delta=None, n=None, return_fields=False,
+                sample_offset=0):
+    """NoiseModeld's arithmetic AND its per-pixel Beta draws for a device batch in one launch: img, background float32 [B,H,W]; grids float32
+    [B,5,gh,gw] (alpha_v, beta_v, alpha_s, beta_s, gamma control points, data/noise_model.py); seed: the 64-bit key of the call's counter-based
+    generator, sample b draws under sample counter sample_offset + b. delta / n (float32 [B,H,W]) replace the drawn Delta / N field.
+    -> float32 [B,H,W]; with return_fields (out, maps [B,5,H,W] -- the four clamped shape maps and Gamma --, fields [B,2,H,W] -- Delta, N)."""
+    assert img.is_cuda and img.dim() == 3 and img.dtype == torch.float32 and background.shape == img.shape and background.dtype == torch.float32
+    assert grids.dim() == 4 and grids.shape[:2] == (img.shape[0], 5) and grids.dtype == torch.float32
+    dev = img.device
+    img, background, grids = img.contiguous(), background.to(dev).contiguous(), grids.to(dev).contiguous()
+    B, H, W = img.shape
+    for f in (delta, n):
+        assert f is None or (f.is_cuda and f.shape == img.shape and f.dtype == torch.float32)
+    delta, n = (f.contiguous() if f is not None else None for f in (delta, n))
+    out = torch.empty_like(img)
+    maps = torch.empty((B, 5, H, W), dtype=torch.float32, device=dev) if return_fields else None
+    fields = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if return_fields else None
+    rc = _native.lib().octa_noise_model(_native.ctx(dev.index), _p(img), _p(background), _p(grids), B, H, W, grids.shape[2], grids.shape[3],
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset) & 0xFFFFFFFF, float(lambda_delta), float(lambda_speckle),
+                                        float(lambda_gamma), _p(delta), _p(n), _p(out), _p(maps), _p(fields), _native.current_stream_ptr())
+    _native.check(rc, "octa_noise_model")
+    return (out, maps, fields) if return_fields else out
