@@ -458,6 +458,25 @@ int octa_noise_model(octa_ctx *ctx, const float *d_img, const float *d_backgroun
                      const float *d_delta_in, const float *d_n_in, float *d_out, float *d_maps, float *d_fields, void *stream);
 void octa_philox4x32_10(const uint32_t *counter4, const uint32_t *key2, uint32_t *out4);
 
+/* Backward of octa_noise_model for adversarial training (reference utils/losses.py ANTLoss, models/noise_model.py with adversarial = True):
+ * d_dgrids float32 [B][5][gh][gw] = d sum(out d_dout) / d grids, d_dout float32 [B][H][W]. The first thirteen arguments after d_dout and the two
+ * injected fields are the forward call's; nothing else is kept from it: Delta and N are regenerated from (seed, sample_offset) by the forward's
+ * own sampler code, bit for bit. The gradient is torch autograd's of the reference's formula: pow (both arguments), maximum (the larger side,
+ * half each at a tie), the clamp of the four shape maps (where the bicubic value is >= 1e-3), the gamma grid's clamp (0 <= g <= 1) and factor
+ * 2 lambda_gamma, the bicubic upsampling's adjoint, and for the two drawn fields the reparameterised gradient of Beta.rsample
+ * (torch._dirichlet_grad + the Dirichlet projection), evaluated in double from the variate's log-odds t so that x = 1 / (1 + e^-t) and
+ * 1 - x = 1 / (1 + e^t) are both accurate; 0 where x is 0 or 1, finite for every input. An injected field (d_delta_in / d_n_in) carries no
+ * gradient to its two grids. Deterministic: no atomics, the same bits for every batch size (sample b = a B = 1 call with sample_offset + b).
+ * H, W <= 2^20 each (and H W <= 2^30 as in the forward).
+ * d_dmaps float32 [B][5][H][W], REQUIRED: workspace between the two launches; afterwards the gradient with respect to the five maps.
+ * Optional (NULL = absent): d_out [B][H][W] the re-run forward's output (= octa_noise_model's); d_maps [B][5][H][W] the maps as in
+ *   octa_noise_model; d_logodds [B][2][H][W] t of Delta and N (0 for an injected field); d_bgrad [B][4][H][W] dDelta/dalpha_v, dDelta/dbeta_v,
+ *   dN/dalpha_s, dN/dbeta_s (0 for an injected field). */
+int octa_noise_model_backward(octa_ctx *ctx, const float *d_dout, const float *d_img, const float *d_background, const float *d_grids, int B, int H,
+                              int W, int gh, int gw, uint64_t seed, uint32_t sample_offset, double lambda_delta, double lambda_speckle,
+                              double lambda_gamma, const float *d_delta_in, const float *d_n_in, float *d_dgrids, float *d_dmaps, float *d_out,
+                              float *d_maps, float *d_logodds, float *d_bgrad, void *stream);
+
 /* First layer of the U-Net (UnetBasicBlock.conv1 of the input block: ONE input channel -> Cout in {8, 16, 32, 64}, 3x3,
  * padding 1, stride 1): d_x [N][H][W] bf16, d_w float32 [Cout][9] (tap = 3r + s), d_y [N][H][W][Cout] bf16; the weight
  * gradient d_dw float32 [Cout][9] (overwritten). Streaming kernels: 9 multiply-adds per output are not matrix-core work.

@@ -298,3 +298,55 @@ def noise_model(img, background, grids, seed, lambda_delta=1, lambda_speckle=0.7
                                         float(lambda_gamma), _p(delta), _p(n), _p(out), _p(maps), _p(fields), _native.current_stream_ptr())
     _native.check(rc, "octa_noise_model")
     return (out, maps, fields) if return_fields else out
+
+
+def noise_model_backward(dout, img, background, grids, seed, lambda_delta=1, lambda_speckle=0.7, lambda_gamma=0.3, delta=None, n=None,
+                         return_intermediates=False, sample_offset=0):
+    """The gradient of sum(noise_model(...) * dout) with respect to `grids` (csrc/noise_model.hip, octa_noise_model_backward): the arguments
+    after dout are the forward call's; Delta and N are regenerated from the seed, nothing is kept from the forward. Deterministic, no atomics.
+    -> dgrids float32 [B,5,gh,gw]; with return_intermediates (dgrids, {"dmaps" [B,5,H,W] the gradient with respect to the five maps, "out"
+    [B,H,W] the re-run forward's output, "maps" [B,5,H,W], "logodds" [B,2,H,W] t = log(x / (1 - x)) of Delta and N, "bgrad" [B,4,H,W]
+    dDelta/dalpha_v, dDelta/dbeta_v, dN/dalpha_s, dN/dbeta_s})."""
+    assert img.is_cuda and img.dim() == 3 and img.dtype == torch.float32 and background.shape == img.shape and background.dtype == torch.float32
+    assert grids.dim() == 4 and grids.shape[:2] == (img.shape[0], 5) and grids.dtype == torch.float32
+    assert dout.shape == img.shape and dout.dtype == torch.float32 and dout.device == img.device
+    dev = img.device
+    dout, img, background, grids = dout.contiguous(), img.contiguous(), background.to(dev).contiguous(), grids.detach().to(dev).contiguous()
+    B, H, W = img.shape
+    for f in (delta, n):
+        assert f is None or (f.is_cuda and f.shape == img.shape and f.dtype == torch.float32)
+    delta, n = (f.contiguous() if f is not None else None for f in (delta, n))
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    dgrids, dmaps = torch.empty_like(grids), new(B, 5, H, W)
+    extra = {"out": new(B, H, W), "maps": new(B, 5, H, W), "logodds": new(B, 2, H, W), "bgrad": new(B, 4, H, W)} if return_intermediates else {}
+    rc = _native.lib().octa_noise_model_backward(_native.ctx(dev.index), _p(dout), _p(img), _p(background), _p(grids), B, H, W, grids.shape[2], grids.shape[3],
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset) & 0xFFFFFFFF, float(lambda_delta),
+                                                 float(lambda_speckle), float(lambda_gamma), _p(delta), _p(n), _p(dgrids), _p(dmaps), _p(extra.get("out")),
+                                                 _p(extra.get("maps")), _p(extra.get("logodds")), _p(extra.get("bgrad")), _native.current_stream_ptr())
+    _native.check(rc, "octa_noise_model_backward")
+    return (dgrids, dict(extra, dmaps=dmaps)) if return_intermediates else dgrids
+
+
+class _NoiseModelRsample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, grids, img, background, seed, lambdas, delta, n, sample_offset):
+        ctx.save_for_backward(grids, img, background, delta, n)
+        ctx.call = (seed, lambdas, sample_offset)
+        return noise_model(img, background, grids.detach(), seed, *lambdas, delta=delta, n=n, sample_offset=sample_offset)
+
+    @staticmethod
+    def backward(ctx, dout):
+        grids, img, background, delta, n = ctx.saved_tensors
+        seed, lambdas, sample_offset = ctx.call
+        dgrids = noise_model_backward(dout.float().contiguous(), img, background, grids, seed, *lambdas, delta=delta, n=n, sample_offset=sample_offset)
+        return dgrids, None, None, None, None, None, None, None
+
+
+def noise_model_rsample(img, background, grids, seed, lambda_delta=1, lambda_speckle=0.7, lambda_gamma=0.3, delta=None, n=None, sample_offset=0):
+    """noise_model(...) as a differentiable function of `grids` (the reference's NoiseModel.forward with Beta.rsample): forward the
+    octa_noise_model launch, backward octa_noise_model_backward, which redraws Delta and N from the seed. The gradient goes to `grids` only.
+    img, background: float32 [B,H,W] on the device, without gradient; grids float32 [B,5,gh,gw] on the same device."""
+    assert not (img.requires_grad or background.requires_grad), "noise_model_rsample differentiates with respect to the control grids only"
+    assert grids.is_cuda and grids.device == img.device
+    return _NoiseModelRsample.apply(grids, img, background, int(seed), (float(lambda_delta), float(lambda_speckle), float(lambda_gamma)), delta, n,
+                                    int(sample_offset))

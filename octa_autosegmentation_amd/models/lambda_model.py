@@ -30,13 +30,17 @@ class LambdaModel(BaseModelABC):
             else:
                 self.loss_function = get_loss_function_by_name(self.loss_name, config)
         if phase == Phase.TRAIN and config[Phase.TRAIN].get("AT", False):
-            raise NotImplementedError("adversarial training (Train.AT, configs *_RA / *_AA) is outside the MI355X hot path")
+            # adversarial augmentation (configs/config_ves_seg-S_AA.yml): models/noise_model_at.py, csrc/noise_model.hip both ways
+            self.at = get_loss_function_by_name("AtLoss", config, scaler, self.loss_function, autocast=self.autocast)
         super().initialize_model_and_optimizer(init_mini_batch, init_weights, config, args, scaler, phase)
 
     def inference(self, mini_batch: Dict[str, Any], post_transformations: Dict[str, Callable], device: torch.device = "cpu",
                   phase: Phase = Phase.TEST) -> Tuple[Output, Dict[str, torch.Tensor]]:
         inputs = mini_batch["image"].to(device, non_blocking=True)
         labels = mini_batch["label"].to(device, non_blocking=True) if phase != Phase.TEST else None
+        if phase == Phase.TRAIN and hasattr(self, "at"):
+            inputs, labels = self.at(self.model, inputs, mini_batch["background"].to(device, non_blocking=True), labels)
+            mini_batch["image"] = inputs
         pred = self.model(inputs).squeeze(-1)
         if phase == Phase.TRAIN:          # the scored sample's post-processing leaves the training stream (base_model_abc.aside)
             with aside(pred.device, pred, labels):

@@ -82,9 +82,19 @@ class LSGANLoss:
         return self.loss(prediction, target)
 
 
-def get_loss_function_by_name(name: str, config=None, *args):
+def _at_loss(config, scaler=None, loss=None, **kwargs):
+    """The reference's ("AtLoss", config, scaler, loss): the adversarial-augmentation loop around `loss` with the keys of Train.AT. The
+    GradScaler is accepted and left alone (bf16 training has none; Train.AT.grad_scale stands for its factor, models/noise_model_at.py)."""
+    from .noise_model_at import AtLoss
+    at = (config or {}).get("Train", {}).get("AT")
+    seed = (config or {}).get("General", {}).get("seed", 42)          # the geometry draws get a stream of their own, seeded like the loader's
+    return AtLoss(loss, **{"seed": int(seed) + 4, **(at if isinstance(at, dict) else {}), **kwargs})
+
+
+def get_loss_function_by_name(name: str, config=None, *args, **kwargs):
     table = {"DiceBCELoss": lambda: DiceBCELoss(True), "LSGANLoss": LSGANLoss,
-             "BCELoss": lambda: torch.nn.BCEWithLogitsLoss(), "MSELoss": torch.nn.MSELoss}
+             "BCELoss": lambda: torch.nn.BCEWithLogitsLoss(), "MSELoss": torch.nn.MSELoss,
+             "AtLoss": lambda: _at_loss(config, *args, **kwargs)}
     if name not in table:
         raise NotImplementedError(f"loss {name} is outside the MI355X hot path")
     return table[name]()
