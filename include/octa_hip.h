@@ -551,6 +551,15 @@ int octa_blur_up_bwd(octa_ctx *ctx, const void *d_in, void *d_out, int dtype, in
 int octa_remove_small_objects(octa_ctx *ctx, const uint8_t *d_in, int B, int H, int W, int min_size, int connectivity,
                               uint8_t on_value, uint8_t *d_out, void *stream);
 
+/* ---- skeletonisation for the clDice metric --------------
+ * Zhang & Suen's 1984 parallel thinning (what skimage.morphology.skeletonize does in 2-D; reference utils/cldice.py) of a batch of
+ * masks in HBM: d_in uint8 [B][H][W] (non-zero = foreground, outside the image = background), d_out uint8 [B][H][W] = 0 / 1, the
+ * fixed point of the (first, second) sub-iterations. d_out must not overlap d_in (-2). Images never influence each other and the
+ * result is the same on every run. Convergence is decided on the device; the call waits on `stream` once per 8 double passes to read
+ * the per-image flags, and returns -3 if H + W + 8 double passes reach no fixed point (a heuristic bound: -3 means "still converging", never a wrong result). passes (host, may be NULL): double passes the
+ * slowest image took, the last one -- which removed nothing -- included. */
+int octa_skeletonize(octa_ctx *ctx, const uint8_t *d_in, int B, int H, int W, uint8_t *d_out, int *passes, void *stream);
+
 /* ---- Optimally Oriented Flux (OOF) baseline (configs/config_oof.yml, reference models/oof.py) ----------
  * Caller-owned device buffers, no context: the workspace is the caller's (size from the *_workspace_bytes functions, a function
  * of the shape only) and must not be shared by two calls in flight. 1 <= h, w <= 4096 (any factorisation; prime factors above 5

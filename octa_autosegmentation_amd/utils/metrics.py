@@ -1,9 +1,8 @@
 """Training / validation metrics of the entry points (reference utils/metrics.py:165-196 MetricsManager): DSC and IoU in
-the training phase; the validation phase adds AUC, ACC, Recall, Precision and -- when scikit-image is importable -- clDice
-(skeletonisation is skimage's; it is not in the MI355X image, so the column is simply absent there). Every score is computed
+the training phase; the validation phase adds clDice, AUC, ACC, Recall and Precision, in the reference's order. Every score is computed
 on the device the tensors live on and read back as ONE scalar per metric and sample; the reference moves whole 1216x1216
-maps to numpy for each of them. These are logging quantities, not a kernel target (metrics are out of
-scope as kernels)."""
+maps to numpy for each of them. clDice's skeletons are a kernel of their own (csrc/skeleton.hip through utils/skeleton.py, DESIGN.md
+4.2k); the other scores are torch reductions -- logging quantities, not a kernel target."""
 import math
 
 import torch
@@ -119,32 +118,37 @@ class AUCMetric(Metric):
 
 
 class ClDiceMetric(Metric):
+    """clDice per sample and layer as the reference's utils/cldice.py:19-35: with s = skeleton (utils/skeleton.py, Zhang-Suen),
+    tprec = sum(v_p * s_l) / sum(s_l), tsens = sum(v_l * s_p) / sum(s_p) -- `v` enters by VALUE, not as a mask --
+    clDice = 2 tprec tsens / (tprec + tsens), 0 / 0 = NaN as numpy gives it (skipped by `aggregate`, the reference's nanmean). The sums
+    are float64 (the reference sums in the maps' dtype, which is the same number for 0 / 1 maps of up to 2^24 pixels).
+    CUDA maps: both skeletons of a sample come from ONE batched call of the kernel (csrc/skeleton.hip), the four sums are device
+    reductions and the score stays a 0-dim device tensor; the only host reads are the kernel's chunked convergence flags. CPU maps take
+    `skeletonize_host`. No CUDA tensor ever takes the host path, so there is nothing to route through the loud-fallback door.
+    3-D layers (the reference's `method="lee"` branch; no config here produces them) raise NotImplementedError.
+    Parity with scikit-image itself is UNPINNED (it is neither installed here nor shipped with the reference): the rule is pinned by
+    the published algorithm, the literal oracle of tests/test_skeleton.py and the known answers there."""
+
     def __call__(self, y_pred, y):
-        from skimage.morphology import skeletonize
-        import numpy as np
+        from .skeleton import skeletonize
         for p_i, y_i in zip(y_pred, y):
             for layer in range(len(p_i)):
-                v_p, v_l = p_i[layer].detach().cpu().numpy(), y_i[layer].detach().cpu().numpy()
-                cl = lambda v, s: np.sum(v * s) / np.sum(s)
-                tprec, tsens = cl(v_p, skeletonize(v_l)), cl(v_l, skeletonize(v_p))
-                self.add(float(2 * tprec * tsens / (tprec + tsens)))
-
-
-def _have_skimage():
-    try:
-        import skimage.morphology  # noqa: F401
-        return True
-    except Exception:
-        return False
+                v_p, v_l = p_i[layer].detach(), y_i[layer].detach()
+                if v_p.dim() != 2:
+                    raise NotImplementedError(f"clDice of a {v_p.dim()}-D layer (shape {tuple(v_p.shape)}): only the 2-D skeleton is implemented, "
+                                              "the reference's 3-D skeletonize(method='lee') is not")
+                dt = torch.promote_types(v_p.dtype, v_l.dtype)          # non-zero stays non-zero; the skeleton takes any dtype
+                s_p, s_l = skeletonize(torch.stack([v_p.to(dt), v_l.to(dt)])).double()
+                tprec = (v_p.double() * s_l).sum() / s_l.sum()
+                tsens = (v_l.double() * s_p).sum() / s_p.sum()
+                self.add(2 * tprec * tsens / (tprec + tsens))
 
 
 class MetricsManager:
     def __init__(self, phase: Phase = Phase.TRAIN):
         self.metrics = {"DSC": MacroDiceMetric(), "IoU": MeanIoU()}
         if phase != Phase.TRAIN:
-            if _have_skimage():
-                self.metrics["ClDice"] = ClDiceMetric()
-            self.metrics.update({"AUC": AUCMetric(), "ACC": AccuracyMetric(), "Recall": Recall(), "Precision": Precision()})
+            self.metrics.update({"ClDice": ClDiceMetric(), "AUC": AUCMetric(), "ACC": AccuracyMetric(), "Recall": Recall(), "Precision": Precision()})
         self.comp = "DSC"
 
     def __call__(self, y_pred, y):
