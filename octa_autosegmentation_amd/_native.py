@@ -188,16 +188,23 @@ def check(rc, what):
 _tls = threading.local()
 
 
-def new_ctx(device_index=None):
-    """A private context (own grow-only scratch); the owner frees it with free_ctx()."""
+def _device_index(device_index):
+    """The GPU to use (None: torch's current device); raises when torch sees none."""
     import torch
     if not torch.cuda.is_available():
         raise OctaHipError("no ROCm GPU visible to torch; the HIP path cannot run (no CPU fallback)")
-    if device_index is None:
-        device_index = torch.cuda.current_device()
+    return int(torch.cuda.current_device() if device_index is None else device_index)
+
+
+def _create_ctx(device_index):
     out = c_void_p()
-    check(lib().octa_ctx_create(int(device_index), ctypes.byref(out)), "octa_ctx_create")
+    call("octa_ctx_create", device_index, ctypes.byref(out))
     return out
+
+
+def new_ctx(device_index=None):
+    """A private context (own grow-only scratch); the owner frees it with free_ctx()."""
+    return _create_ctx(_device_index(device_index))
 
 
 def free_ctx(h):
@@ -225,25 +232,50 @@ def ctx(device_index=None):
     import torch
     if getattr(_tls, "ctx", None) is not None:
         return _tls.ctx
-    if not torch.cuda.is_available():
-        raise OctaHipError("no ROCm GPU visible to torch; the HIP path cannot run (no CPU fallback)")
-    if device_index is None:
-        device_index = torch.cuda.current_device()
-    key = (int(device_index), threading.get_ident(), torch.cuda.current_stream(int(device_index)).cuda_stream)
+    device_index = _device_index(device_index)
+    key = (device_index, threading.get_ident(), torch.cuda.current_stream(device_index).cuda_stream)
     with _lock:
         h = _ctxs.get(key)
     if h is None:
-        out = c_void_p()
-        check(lib().octa_ctx_create(int(device_index), ctypes.byref(out)), "octa_ctx_create")
+        h = _create_ctx(device_index)
         with _lock:
-            _ctxs[key] = out
-        h = out
+            _ctxs[key] = h
     return h
 
 
 def current_stream_ptr():
     import torch
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def addr(t):
+    """Device (or host) address of a tensor for a pointer field of an argument struct; None stays None."""
+    return t.data_ptr() if t is not None else None
+
+
+def _ctx_of(device):       # launch() has a parameter called ctx
+    return ctx(device.index)
+
+
+# The marshalling rule of launch() and call(): an argument with a data_ptr attribute (a torch tensor) becomes its address; everything
+# else -- None, Python numbers, ctypes.byref(), ctypes structs, bytes, numpy `.ctypes.data` ints -- goes through untouched and the
+# declared argtypes (SIGNATURES) convert it.
+
+def launch(name, device, *args, what=None, ctx=None, stream=None):
+    """Call `int name(octa_ctx*, args..., void* stream)` and check its return code. The context is the one of `device` for the
+    calling thread and current stream (ctx()) and the stream is torch's current one; ctx= / stream= name another (a private context
+    from new_ctx(), a stream of the caller's own). what= replaces the symbol's name in the error message."""
+    argv = [_ctx_of(device) if ctx is None else ctx]
+    for a in args:
+        argv.append(a.data_ptr() if hasattr(a, "data_ptr") else a)
+    argv.append(current_stream_ptr() if stream is None else stream)
+    check(getattr(lib(), name)(*argv), what or name)
+
+
+def call(name, *args, what=None):
+    """Call `int name(args...)` -- an entry point that is not of launch()'s form: no context and no stream, or only one of the two,
+    which then is an ordinary argument -- and check its return code. Entry points that return a VALUE are called through lib()."""
+    check(getattr(lib(), name)(*[a.data_ptr() if hasattr(a, "data_ptr") else a for a in args]), what or name)
 
 
 def advance_python_random(n):
@@ -256,5 +288,5 @@ def advance_python_random(n):
         return
     ver, state, gauss = _random.getstate()
     arr = np.array(state, dtype=np.uint32)
-    check(lib().octa_py_random_advance(arr.ctypes.data, int(n)), "octa_py_random_advance")
+    call("octa_py_random_advance", arr.ctypes.data, int(n))
     _random.setstate((ver, tuple(arr.tolist()), gauss))

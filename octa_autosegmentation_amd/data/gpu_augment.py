@@ -11,16 +11,11 @@ decisions are drawn on the host from one numpy RandomState in the order MONAI's 
 sample share them. MONAI is not installed here: its per-transform random streams are not reproduced (parity unpinned),
 the geometry is pinned against the torch ops MONAI delegates to (tests/test_augment_gpu.py).
 """
-import ctypes
 
 import numpy as np
 import torch
 
 from .. import _native
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def resize_bilinear(x, size, mul=None, add=None):
@@ -29,9 +24,7 @@ def resize_bilinear(x, size, mul=None, add=None):
     assert x.is_cuda and x.dim() == 3 and x.is_contiguous() and x.dtype in (torch.uint8, torch.float32)
     B, h, w = x.shape
     out = torch.empty((B, int(size[0]), int(size[1])), dtype=torch.float32, device=x.device)
-    rc = _native.lib().octa_resize_bilinear(_native.ctx(x.device.index), _p(x), 0 if x.dtype == torch.uint8 else 1, B, h, w, _p(out),
-                                            out.shape[1], out.shape[2], _p(mul), _p(add), _native.current_stream_ptr())
-    _native.check(rc, "octa_resize_bilinear")
+    _native.launch("octa_resize_bilinear", x.device, x, 0 if x.dtype == torch.uint8 else 1, B, h, w, out, out.shape[1], out.shape[2], mul, add)
     return out
 
 
@@ -40,8 +33,7 @@ def resize_bilinear_bwd(dy, size):
     assert dy.is_cuda and dy.dim() == 3 and dy.is_contiguous() and dy.dtype == torch.float32
     B, H, W = dy.shape
     dx = torch.empty((B, int(size[0]), int(size[1])), dtype=torch.float32, device=dy.device)
-    rc = _native.lib().octa_resize_bilinear_bwd(_native.ctx(dy.device.index), _p(dy), B, dx.shape[1], dx.shape[2], H, W, _p(dx), _native.current_stream_ptr())
-    _native.check(rc, "octa_resize_bilinear_bwd")
+    _native.launch("octa_resize_bilinear_bwd", dy.device, dy, B, dx.shape[1], dx.shape[2], H, W, dx)
     return dx
 
 
@@ -66,10 +58,8 @@ def flip_rot90_rotate(x, angle, rot_k=None, flip=None, threshold=None):
     """x: CUDA float32 [B,N,N]; angle float32 [B] (radians), rot_k / flip int32 [B] or None."""
     assert x.is_cuda and x.dim() == 3 and x.shape[1] == x.shape[2] and x.dtype == torch.float32 and x.is_contiguous()
     out = torch.empty_like(x)
-    rc = _native.lib().octa_flip_rot90_rotate(_native.ctx(x.device.index), _p(x), _p(out), x.shape[0], x.shape[1], _p(angle), _p(rot_k), _p(flip),
-                                              float(threshold if threshold is not None else 0.0), 0 if threshold is None else 1,
-                                              _native.current_stream_ptr())
-    _native.check(rc, "octa_flip_rot90_rotate")
+    _native.launch("octa_flip_rot90_rotate", x.device, x, out, x.shape[0], x.shape[1], angle, rot_k, flip, float(threshold if threshold is not None else 0.0),
+                   0 if threshold is None else 1)
     return out
 
 
@@ -79,9 +69,8 @@ def background_noise(img, noise, u, out_dtype=torch.float64):
     assert img.is_cuda and img.shape == noise.shape == u.shape and u.dtype == torch.float64
     img, noise, u = img.contiguous().float(), noise.contiguous().float(), u.contiguous()
     out = torch.empty(img.shape, dtype=out_dtype, device=img.device)
-    o64, o32 = (_p(out), None) if out_dtype == torch.float64 else (None, _p(out))
-    rc = _native.lib().octa_background_noise(_native.ctx(img.device.index), _p(img), _p(noise), _p(u), img.numel(), o64, o32, _native.current_stream_ptr())
-    _native.check(rc, "octa_background_noise")
+    o64, o32 = (out, None) if out_dtype == torch.float64 else (None, out)
+    _native.launch("octa_background_noise", img.device, img, noise, u, img.numel(), o64, o32)
     return out
 
 
@@ -91,9 +80,7 @@ def speckle_brightness(img, grid9, u):
     img, grid9, u = img.contiguous().float(), grid9.contiguous().float(), u.contiguous().float()
     out = torch.empty_like(img)
     mm = torch.empty((img.shape[0], 2), dtype=torch.int32, device=img.device)
-    rc = _native.lib().octa_speckle_brightness(_native.ctx(img.device.index), _p(img), _p(grid9), _p(u), img.shape[0], img.shape[1], img.shape[2],
-                                               _p(out), _p(mm), _native.current_stream_ptr())
-    _native.check(rc, "octa_speckle_brightness")
+    _native.launch("octa_speckle_brightness", img.device, img, grid9, u, img.shape[0], img.shape[1], img.shape[2], out, mm)
     return out
 
 
@@ -200,10 +187,8 @@ def menten_vessel_noise(img, bernoulli, quantum, sigma=1.0, scaling=0.5, r=48):
     B, H, W = img.shape
     tmp = torch.empty((B, H, W), dtype=torch.float64, device=img.device)
     out = torch.empty_like(tmp)
-    rc = _native.lib().octa_menten_vessel_noise(_native.ctx(img.device.index), _p(img), 0 if img.dtype == torch.float32 else 1, _p(bernoulli), _p(quantum),
-                                                _p(w), (w.numel() - 1) // 2, float(scaling), float(r), B, H, W, _p(tmp), _p(out),
-                                                _native.current_stream_ptr())
-    _native.check(rc, "octa_menten_vessel_noise")
+    _native.launch("octa_menten_vessel_noise", img.device, img, 0 if img.dtype == torch.float32 else 1, bernoulli, quantum, w, (w.numel() - 1) // 2,
+                   float(scaling), float(r), B, H, W, tmp, out)
     return out
 
 
@@ -225,9 +210,7 @@ def menten_floater_mask(points, dilations, N, device):
     B = pts.shape[0]
     mask = torch.empty((B, N, N), dtype=torch.uint8, device=device)
     dist = torch.empty((B, N, N), dtype=torch.int32, device=device)
-    rc = _native.lib().octa_menten_floater_mask(_native.ctx(mask.device.index), _p(pts), _p(npts), _p(dil), B, P, N, _p(mask), _p(dist),
-                                                _native.current_stream_ptr())
-    _native.check(rc, "octa_menten_floater_mask")
+    _native.launch("octa_menten_floater_mask", mask.device, pts, npts, dil, B, P, N, mask, dist)
     return mask.bool()
 
 
@@ -243,9 +226,7 @@ def menten_floater(img, points, dilations, sigma=10):
     dist = torch.empty((B, N, N), dtype=torch.int32, device=img.device)
     tmp = torch.empty_like(img)
     out = torch.empty_like(img)
-    rc = _native.lib().octa_menten_floater(_native.ctx(img.device.index), _p(img), _p(pts), _p(npts), _p(dil), _p(w), (w.numel() - 1) // 2, B, P, N,
-                                           _p(mask), _p(dist), _p(tmp), _p(out), _native.current_stream_ptr())
-    _native.check(rc, "octa_menten_floater")
+    _native.launch("octa_menten_floater", img.device, img, pts, npts, dil, w, (w.numel() - 1) // 2, B, P, N, mask, dist, tmp, out)
     return out
 
 
@@ -268,9 +249,7 @@ def menten_motion(x, table, white=None):
         assert d_white.shape[1] == W
     d_table = torch.from_numpy(table).to(x.device)
     out = torch.empty_like(x)
-    rc = _native.lib().octa_menten_motion(_native.ctx(x.device.index), _p(x), _p(out), esz, _p(d_table), _p(d_white), n_white, unit, B, H, W,
-                                          _native.current_stream_ptr())
-    _native.check(rc, "octa_menten_motion")
+    _native.launch("octa_menten_motion", x.device, x, out, esz, d_table, d_white, n_white, unit, B, H, W)
     return out
 
 
@@ -293,10 +272,8 @@ def noise_model(img, background, grids, seed, lambda_delta=1, lambda_speckle=0.7
     out = torch.empty_like(img)
     maps = torch.empty((B, 5, H, W), dtype=torch.float32, device=dev) if return_fields else None
     fields = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if return_fields else None
-    rc = _native.lib().octa_noise_model(_native.ctx(dev.index), _p(img), _p(background), _p(grids), B, H, W, grids.shape[2], grids.shape[3],
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset) & 0xFFFFFFFF, float(lambda_delta), float(lambda_speckle),
-                                        float(lambda_gamma), _p(delta), _p(n), _p(out), _p(maps), _p(fields), _native.current_stream_ptr())
-    _native.check(rc, "octa_noise_model")
+    _native.launch("octa_noise_model", dev, img, background, grids, B, H, W, grids.shape[2], grids.shape[3], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                   int(sample_offset) & 0xFFFFFFFF, float(lambda_delta), float(lambda_speckle), float(lambda_gamma), delta, n, out, maps, fields)
     return (out, maps, fields) if return_fields else out
 
 
@@ -319,11 +296,9 @@ def noise_model_backward(dout, img, background, grids, seed, lambda_delta=1, lam
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     dgrids, dmaps = torch.empty_like(grids), new(B, 5, H, W)
     extra = {"out": new(B, H, W), "maps": new(B, 5, H, W), "logodds": new(B, 2, H, W), "bgrad": new(B, 4, H, W)} if return_intermediates else {}
-    rc = _native.lib().octa_noise_model_backward(_native.ctx(dev.index), _p(dout), _p(img), _p(background), _p(grids), B, H, W, grids.shape[2], grids.shape[3],
-                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset) & 0xFFFFFFFF, float(lambda_delta),
-                                                 float(lambda_speckle), float(lambda_gamma), _p(delta), _p(n), _p(dgrids), _p(dmaps), _p(extra.get("out")),
-                                                 _p(extra.get("maps")), _p(extra.get("logodds")), _p(extra.get("bgrad")), _native.current_stream_ptr())
-    _native.check(rc, "octa_noise_model_backward")
+    _native.launch("octa_noise_model_backward", dev, dout, img, background, grids, B, H, W, grids.shape[2], grids.shape[3], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                   int(sample_offset) & 0xFFFFFFFF, float(lambda_delta), float(lambda_speckle), float(lambda_gamma), delta, n, dgrids, dmaps, extra.get("out"),
+                   extra.get("maps"), extra.get("logodds"), extra.get("bgrad"))
     return (dgrids, dict(extra, dmaps=dmaps)) if return_intermediates else dgrids
 
 

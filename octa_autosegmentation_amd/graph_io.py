@@ -47,7 +47,7 @@ def write_csv(edges, path):
     """`<name>.csv` of generate_vessel_graph.py:59-66, formatted and written natively (the GIL is released for the call)."""
     from . import _native
     e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1, 7)
-    _native.check(_native.lib().octa_csv_write_file(str(path).encode(), e.ctypes.data, len(e)), "octa_csv_write_file")
+    _native.call("octa_csv_write_file", str(path).encode(), e.ctypes.data, len(e))
 
 
 def parse_legacy_position(s):
@@ -138,10 +138,7 @@ def edges_as_read_back_device(d_edges):
         raise ValueError("d_edges must be a contiguous float64 CUDA tensor")
     out = torch.empty_like(d_edges)
     bad = ctypes.c_int(0)
-    rc = _native.lib().octa_edges_read_back(_native.ctx(d_edges.device.index), ctypes.c_void_p(d_edges.data_ptr()),
-                                            ctypes.c_void_p(out.data_ptr()), d_edges.shape[0], ctypes.byref(bad),
-                                            _native.current_stream_ptr())
-    _native.check(rc, "octa_edges_read_back")
+    _native.launch("octa_edges_read_back", d_edges.device, d_edges, out, d_edges.shape[0], ctypes.byref(bad))
     if bad.value:
         out = torch.from_numpy(edges_as_read_back(d_edges.cpu().numpy())).to(d_edges.device)
     return out

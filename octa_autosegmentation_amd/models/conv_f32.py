@@ -44,11 +44,8 @@ def _packed(weight, transposed):
 
 def _launch(x, wp, wp_offset, bias, y, Cout, cout_w, K, stride, pad, Ho, Wo, osc=1, ooy=0, oox=0):
     N, Cin, H, W = x.shape
-    rc = _native.lib().octa_conv2d_f32_nchw(
-        _native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(wp.data_ptr() + 4 * wp_offset),
-        ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(y.data_ptr()),
-        N, Cin, H, W, Cout, cout_w, K, stride, pad, Ho, Wo, osc, ooy, oox, _native.current_stream_ptr())
-    _native.check(rc, "octa_conv2d_f32_nchw")
+    _native.launch("octa_conv2d_f32_nchw", x.device, x, wp.data_ptr() + 4 * wp_offset, bias, y,
+                   N, Cin, H, W, Cout, cout_w, K, stride, pad, Ho, Wo, osc, ooy, oox)
 
 
 def supported(conv):
@@ -85,10 +82,7 @@ def forward(conv, x):
         wp = _packed(conv.weight, True)
         y = torch.empty((N, Cout, H * k, W * k), dtype=torch.float32, device=x.device)
         if k == 2:          # one launch, both output parities of a row pair written as 8-byte pairs
-            rc = _native.lib().octa_convtranspose2x2_f32_nchw(
-                _native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(wp.data_ptr()), ctypes.c_void_p(y.data_ptr()),
-                N, Cin, H, W, Cout, _native.current_stream_ptr())
-            _native.check(rc, "octa_convtranspose2x2_f32_nchw")
+            _native.launch("octa_convtranspose2x2_f32_nchw", x.device, x, wp, y, N, Cin, H, W, Cout)
             return y
         for a in range(k):
             for b in range(k):
@@ -178,10 +172,7 @@ def dgrad(conv, gy, x_shape):
     Cout, Ho, Wo = gy.shape[1], gy.shape[2], gy.shape[3]
     wd = _packed_dgrad(conv.weight, kind)
     dx = torch.empty((N, Cin, H, W), dtype=torch.float32, device=gy.device)
-    rc = _native.lib().octa_conv2d_f32_dgrad_nchw(
-        _native.ctx(gy.device.index), ctypes.c_void_p(gy.data_ptr()), ctypes.c_void_p(wd.data_ptr()), ctypes.c_void_p(dx.data_ptr()),
-        N, Cin, H, W, Cout, K, s, pad, Ho, Wo, int(transposed), _native.current_stream_ptr())
-    _native.check(rc, "octa_conv2d_f32_dgrad_nchw")
+    _native.launch("octa_conv2d_f32_dgrad_nchw", gy.device, gy, wd, dx, N, Cin, H, W, Cout, K, s, pad, Ho, Wo, int(transposed))
     return dx
 
 
@@ -193,16 +184,11 @@ def wgrad(conv, x, gy, want_bias):
     N, Cin, H, W = a.shape
     Cout, Ho, Wo = b.shape[1], b.shape[2], b.shape[3]
     nbytes = ctypes.c_size_t(0)
-    _native.check(_native.lib().octa_conv2d_f32_wgrad_workspace(N, Cin, H, W, Cout, K, s, pad, Ho, Wo, ctypes.byref(nbytes)),
-                  "octa_conv2d_f32_wgrad_workspace")
+    _native.call("octa_conv2d_f32_wgrad_workspace", N, Cin, H, W, Cout, K, s, pad, Ho, Wo, ctypes.byref(nbytes))
     ws = torch.empty(max(nbytes.value, 4), dtype=torch.uint8, device=x.device)
     dw = torch.empty((Cout, Cin, K, K), dtype=torch.float32, device=x.device)
     db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
-    rc = _native.lib().octa_conv2d_f32_wgrad_nchw(
-        _native.ctx(x.device.index), ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), ctypes.c_void_p(dw.data_ptr()),
-        ctypes.c_void_p(db.data_ptr()) if db is not None else None, ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-        N, Cin, H, W, Cout, K, s, pad, Ho, Wo, _native.current_stream_ptr())
-    _native.check(rc, "octa_conv2d_f32_wgrad_nchw")
+    _native.launch("octa_conv2d_f32_wgrad_nchw", x.device, a, b, dw, db, ws, ws.numel(), N, Cin, H, W, Cout, K, s, pad, Ho, Wo)
     return dw, db
 
 

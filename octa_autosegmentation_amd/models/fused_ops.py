@@ -1,6 +1,4 @@
 """torch.autograd bindings of the hand-written HIP kernels used by the training step."""
-import ctypes
-
 import torch
 
 from .. import _native
@@ -18,12 +16,7 @@ class _InstNormLReLU(torch.autograd.Function):
         rstd = torch.empty_like(mean)
         w = weight.float().contiguous() if weight is not None else None
         b = bias.float().contiguous() if bias is not None else None
-        rc = _native.lib().octa_instnorm_lrelu_fwd(
-            _native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()),
-            ctypes.c_void_p(w.data_ptr()) if w is not None else None, ctypes.c_void_p(b.data_ptr()) if b is not None else None,
-            ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(rstd.data_ptr()), B, C, hw, dtype, float(slope), float(eps),
-            _native.current_stream_ptr())
-        _native.check(rc, "octa_instnorm_lrelu_fwd")
+        _native.launch("octa_instnorm_lrelu_fwd", x.device, x, y, w, b, mean, rstd, B, C, hw, dtype, float(slope), float(eps))
         ctx.save_for_backward(x, w, b, mean, rstd)
         ctx.slope, ctx.has_w, ctx.has_b = float(slope), weight is not None, bias is not None
         ctx.w_dtype = weight.dtype if weight is not None else None
@@ -41,10 +34,7 @@ class _InstNormLReLU(torch.autograd.Function):
         dx = torch.empty_like(x)
         dw = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_w else None
         db = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_b else None
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        rc = _native.lib().octa_instnorm_lrelu_bwd(_native.ctx(x.device.index), p(x), p(dy), p(w), p(b), p(mean), p(rstd), p(dx), p(dw), p(db),
-                                                   B, C, hw, dtype, ctx.slope, _native.current_stream_ptr())
-        _native.check(rc, "octa_instnorm_lrelu_bwd")
+        _native.launch("octa_instnorm_lrelu_bwd", x.device, x, dy, w, b, mean, rstd, dx, dw, db, B, C, hw, dtype, ctx.slope)
         return dx, (dw.to(ctx.w_dtype) if dw is not None else None), (db.to(ctx.w_dtype) if db is not None else None), None, None
 
 

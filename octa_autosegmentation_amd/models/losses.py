@@ -21,39 +21,29 @@ class _FusedDiceBCE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, y, smooth_nr, smooth_dr):
-        import ctypes
         from .. import _native
         x = logits.contiguous()
         t = y.contiguous().float()
         B = x.shape[0]
         n = x.numel() // B
         sums = torch.empty((B, 4), dtype=torch.float64, device=x.device)
-        p = lambda a: ctypes.c_void_p(a.data_ptr())
-        rc = _native.lib().octa_dice_bce_fwd(_native.ctx(x.device.index), p(x), 0 if x.dtype == torch.float32 else 1, p(t), B, n, p(sums),
-                                             _native.current_stream_ptr())
-        _native.check(rc, "octa_dice_bce_fwd")
+        _native.launch("octa_dice_bce_fwd", x.device, x, 0 if x.dtype == torch.float32 else 1, t, B, n, sums)
         # (dice + bce) / 2 with dice = mean(1 - (2 s0 + nr) / (s1 + s2 + dr)), bce = sum(s3) / (B n): one scalar launch, double arithmetic
         loss = torch.empty((), dtype=torch.float32, device=x.device)
-        rc = _native.lib().octa_dice_bce_finish(_native.ctx(x.device.index), p(sums), B, n, float(smooth_nr), float(smooth_dr), p(loss),
-                                                _native.current_stream_ptr())
-        _native.check(rc, "octa_dice_bce_finish")
+        _native.launch("octa_dice_bce_finish", x.device, sums, B, n, float(smooth_nr), float(smooth_dr), loss)
         ctx.save_for_backward(x, t, sums)
         ctx.smooth = (float(smooth_nr), float(smooth_dr))
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
         from .. import _native
         x, t, sums = ctx.saved_tensors
         B = x.shape[0]
         n = x.numel() // B
         dx = torch.empty_like(x)
         gg = g.reshape(1).float().contiguous()
-        p = lambda a: ctypes.c_void_p(a.data_ptr())
-        rc = _native.lib().octa_dice_bce_bwd(_native.ctx(x.device.index), p(x), 0 if x.dtype == torch.float32 else 1, p(t), B, n, p(sums), p(gg),
-                                             ctx.smooth[0], ctx.smooth[1], p(dx), _native.current_stream_ptr())
-        _native.check(rc, "octa_dice_bce_bwd")
+        _native.launch("octa_dice_bce_bwd", x.device, x, 0 if x.dtype == torch.float32 else 1, t, B, n, sums, gg, ctx.smooth[0], ctx.smooth[1], dx)
         return dx, None, None, None
 
 

@@ -16,12 +16,10 @@ def _pad32(c):
     return (c + 31) // 32 * 32
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _addr(t):
-    return t.data_ptr() if t is not None else None
+def _bf16c(t):
+    """Contiguous bfloat16 (the form every backward kernel reads its incoming gradient in)."""
+    t = t.contiguous()
+    return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
 
 
 def _conv3x3_fwd(x, wt, y, x2=None, y2=None, stride=1, in_dilation=1, tap_mask=0x1ff, scatter=(1, 0, 0), norm=(None, None, None, None), slope=0.0,
@@ -30,14 +28,15 @@ def _conv3x3_fwd(x, wt, y, x2=None, y2=None, stride=1, in_dilation=1, tap_mask=0
     (out_scale, out_off_y, out_off_x); norm = (scale1, shift1, scale2, shift2) of the normalise-on-load inputs; stat_partials float32
     [N][tiles][Cout][2] / stat_slots double [nslot][N][Cout][2] receive the InstanceNorm sums of the result; residual is added in the epilogue."""
     n, h, w, c1 = x.shape
+    ad = _native.addr
     a = _native.Conv3x3Args(
         struct_size=ctypes.sizeof(_native.Conv3x3Args), N=n, H=h, W=w, Cin=c1 + (x2.shape[3] if x2 is not None else 0),
         Cout=y.shape[3] + (y2.shape[3] if y2 is not None else 0), stride=int(stride), in_dilation=int(in_dilation), tap_mask=int(tap_mask),
         out_scale=int(scatter[0]), out_off_y=int(scatter[1]), out_off_x=int(scatter[2]), C1=c1, CY1=y.shape[3],
-        nslot=stat_slots.shape[0] if stat_slots is not None else 0, slope=float(slope), d_x=_addr(x), d_x2=_addr(x2), d_w=_addr(wt), d_y=_addr(y),
-        d_y2=_addr(y2), d_scale1=_addr(norm[0]), d_shift1=_addr(norm[1]), d_scale2=_addr(norm[2]), d_shift2=_addr(norm[3]),
-        d_stat_partials=_addr(stat_partials), d_stat_slots=_addr(stat_slots), d_residual=_addr(residual))
-    _native.check(_native.lib().octa_conv3x3_nhwc_fwd(_native.ctx(x.device.index), ctypes.byref(a), _native.current_stream_ptr()), what)
+        nslot=stat_slots.shape[0] if stat_slots is not None else 0, slope=float(slope), d_x=ad(x), d_x2=ad(x2), d_w=ad(wt), d_y=ad(y),
+        d_y2=ad(y2), d_scale1=ad(norm[0]), d_shift1=ad(norm[1]), d_scale2=ad(norm[2]), d_shift2=ad(norm[3]),
+        d_stat_partials=ad(stat_partials), d_stat_slots=ad(stat_slots), d_residual=ad(residual))
+    _native.launch("octa_conv3x3_nhwc_fwd", x.device, ctypes.byref(a), what=what)
 
 
 def _conv3x3_wgrad(x1, dy, x2=None, into=None, accumulate=False, stride=1, tap_mask=0x1ff, norm=(None, None, None, None), slope=0.0):
@@ -48,11 +47,12 @@ def _conv3x3_wgrad(x1, dy, x2=None, into=None, accumulate=False, stride=1, tap_m
     cin, cout = c1 + (x2.shape[3] if x2 is not None else 0), dy.shape[3]
     dw = into if into is not None else torch.empty((9, cout, cin), dtype=torch.float32, device=x1.device)
     mode = _native.WGRAD_TAP_MAJOR if into is None else (_native.WGRAD_PARAM_ADD if accumulate else _native.WGRAD_PARAM_SET)
+    ad = _native.addr
     a = _native.Conv3x3WgradArgs(
         struct_size=ctypes.sizeof(_native.Conv3x3WgradArgs), N=n, H=h, W=w, Cin=cin, Cout=cout, stride=int(stride), tap_mask=int(tap_mask), C1=c1,
-        out_mode=mode, slope=float(slope), d_x=_addr(x1), d_x2=_addr(x2), d_dy=_addr(dy), d_dw=_addr(dw), d_scale1=_addr(norm[0]),
-        d_shift1=_addr(norm[1]), d_scale2=_addr(norm[2]), d_shift2=_addr(norm[3]))
-    _native.check(_native.lib().octa_conv3x3_nhwc_wgrad(_native.ctx(x1.device.index), ctypes.byref(a), _native.current_stream_ptr()), "octa_conv3x3_nhwc_wgrad")
+        out_mode=mode, slope=float(slope), d_x=ad(x1), d_x2=ad(x2), d_dy=ad(dy), d_dw=ad(dw), d_scale1=ad(norm[0]),
+        d_shift1=ad(norm[1]), d_scale2=ad(norm[2]), d_shift2=ad(norm[3]))
+    _native.launch("octa_conv3x3_nhwc_wgrad", x1.device, ctypes.byref(a))
     return None if into is not None else dw.view(3, 3, cout, cin).permute(2, 3, 0, 1)
 
 
@@ -167,9 +167,7 @@ class WeightPackPlan:
             self.table = torch.tensor(rows, dtype=torch.int64).to(self.device)
             self.ptrs, self.versions = ptrs, None
         if versions != self.versions:
-            rc = _native.lib().octa_pack_conv_weights(_native.ctx(self.device.index), ctypes.c_void_p(self.table.data_ptr()), len(self.params),
-                                                      ctypes.c_void_p(self.buf.data_ptr()), _native.current_stream_ptr())
-            _native.check(rc, "octa_pack_conv_weights")
+            _native.launch("octa_pack_conv_weights", self.device, self.table, len(self.params), self.buf)
             self.versions = versions
 
     def invalidate(self):
@@ -301,10 +299,7 @@ def conv3x3_s2t_nhwc(x, wt, tap_mask=0x1ff, residual=None):
     y = torch.empty((n, 2 * h, 2 * w, cout), dtype=torch.bfloat16, device=x.device)
     if residual is not None:
         assert residual.shape == y.shape and residual.dtype == torch.bfloat16 and residual.is_contiguous()
-    rc = _native.lib().octa_conv3x3_s2t_nhwc(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(wt.data_ptr()),
-                                             ctypes.c_void_p(y.data_ptr()), n, h, w, cin, cout, int(tap_mask),
-                                             ctypes.c_void_p(residual.data_ptr()) if residual is not None else None, _native.current_stream_ptr())
-    _native.check(rc, "octa_conv3x3_s2t_nhwc")
+    _native.launch("octa_conv3x3_s2t_nhwc", x.device, x, wt, y, n, h, w, cin, cout, int(tap_mask), residual)
     return y
 
 
@@ -477,9 +472,7 @@ class _Conv3x3NHWC(torch.autograd.Function):
         xp, weight = ctx.saved_tensors
         if dy is None:
             return None, None, None, None, None
-        dy = dy.contiguous()
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _bf16c(dy)
         cin, st = ctx.cin, ctx.stride
         dx = dw = None
         if ctx.needs_input_grad[0]:
@@ -527,9 +520,7 @@ class _Conv3x3ReflectNHWC(torch.autograd.Function):
         y = torch.empty((n, h, w, cout), dtype=torch.bfloat16, device=x.device)
         wt = pack_weight(weight, cin)
         part = _stat_slots(x.device, n, cout) if want_stats else None       # InstanceNorm statistics from the epilogue (slot form, as conv3x3)
-        rc = _native.lib().octa_conv3x3_nhwc_fwd_pad(_native.ctx(x.device.index), _p(x), _p(wt), _p(y), n, h, w, cin, cout, 1, 1, _p(part),
-                                                     STAT_SLOTS if part is not None else 0, _native.current_stream_ptr())
-        _native.check(rc, "octa_conv3x3_nhwc_fwd_pad")
+        _native.launch("octa_conv3x3_nhwc_fwd_pad", x.device, x, wt, y, n, h, w, cin, cout, 1, 1, part, STAT_SLOTS if part is not None else 0)
         ctx.save_for_backward(x, weight)
         if want_stats:
             ctx.mark_non_differentiable(part)
@@ -542,25 +533,19 @@ class _Conv3x3ReflectNHWC(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         if dy is None:
             return None, None, None
-        dy = dy.contiguous()
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _bf16c(dy)
         n, h, w, cin = x.shape
         cout = dy.shape[3]
-        lib, hctx = _native.lib(), _native.ctx(x.device.index)
         dx = dw = None
         if ctx.needs_input_grad[0]:
             wd = pack_weight_dgrad(weight, cin)
             dxp = torch.empty((n, h + 2, w + 2, cin), dtype=torch.bfloat16, device=x.device)
-            rc = lib.octa_conv3x3_nhwc_fwd_pad(hctx, _p(dy), _p(wd), _p(dxp), n, h, w, cout, cin, 2, 0, None, 0, _native.current_stream_ptr())
-            _native.check(rc, "octa_conv3x3_nhwc_fwd_pad")
+            _native.launch("octa_conv3x3_nhwc_fwd_pad", x.device, dy, wd, dxp, n, h, w, cout, cin, 2, 0, None, 0)
             dx = torch.empty_like(x)
             resample._launch("octa_reflect_pad_bwd", dxp, dx, n, h, w, cin, 1)
         if ctx.needs_input_grad[1]:
             def wgrad_pad(d_dw, out_mode):
-                rc = lib.octa_conv3x3_nhwc_wgrad_pad(_native.ctx(x.device.index), _p(x), _p(dy), _p(d_dw), n, h, w, cin, cout, 1, 1, out_mode,
-                                                     _native.current_stream_ptr())
-                _native.check(rc, "octa_conv3x3_nhwc_wgrad_pad")
+                _native.launch("octa_conv3x3_nhwc_wgrad_pad", x.device, x, dy, d_dw, n, h, w, cin, cout, 1, 1, out_mode)
 
             def wg():
                 dwf = torch.empty((9, cout, cin), dtype=torch.float32, device=x.device)
@@ -604,9 +589,7 @@ class _Conv3x3C1(torch.autograd.Function):
         wf = weight.reshape(cout, 9).float().contiguous()
         y = torch.empty((n, h, w, cout), dtype=torch.bfloat16, device=x.device)
         part = _stat_slots(x.device, n, cout) if want_stats else None
-        rc = _native.lib().octa_conv3x3_c1_fwd(_native.ctx(x.device.index), _p(x), _p(wf), _p(y), n, h, w, cout, _p(part),
-                                               STAT_SLOTS if part is not None else 0, _native.current_stream_ptr())
-        _native.check(rc, "octa_conv3x3_c1_fwd")
+        _native.launch("octa_conv3x3_c1_fwd", x.device, x, wf, y, n, h, w, cout, part, STAT_SLOTS if part is not None else 0)
         ctx.save_for_backward(x)
         ctx.w_shape, ctx.w_dtype = weight.shape, weight.dtype
         ctx.weight_ref = weight
@@ -621,24 +604,18 @@ class _Conv3x3C1(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         if dy is None:
             return None, None, None
-        dy = dy.contiguous()
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _bf16c(dy)
         n, h, w, _ = x.shape
         cout = dy.shape[3]
         def wg():
             dw = torch.empty((cout, 9), dtype=torch.float32, device=x.device)
-            rc = _native.lib().octa_conv3x3_c1_wgrad(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(dy.data_ptr()),
-                                                     ctypes.c_void_p(dw.data_ptr()), n, h, w, cout, _native.current_stream_ptr())
-            _native.check(rc, "octa_conv3x3_c1_wgrad")
+            _native.launch("octa_conv3x3_c1_wgrad", x.device, x, dy, dw, n, h, w, cout)
             return dw.view(ctx.w_shape).to(ctx.w_dtype)
         dx = None
         if ctx.needs_input_grad[0]:
             # dx[n][y][x] = sum_co sum_t dy[n][y + 1 - ky][x + 1 - kx][co] * w[co][t]: the C -> 1 convolution of dy with the flipped kernel, pad K - 1 - 1
             dx = torch.empty((n, h, w, 1), dtype=torch.bfloat16, device=x.device)
-            rc = _native.lib().octa_thinconv_squeeze(_native.ctx(x.device.index), ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(ctx.wf.data_ptr()), None,
-                                                     ctypes.c_void_p(dx.data_ptr()), n, h, w, cout, 3, 1, 1, _native.current_stream_ptr())
-            _native.check(rc, "octa_thinconv_squeeze")
+            _native.launch("octa_thinconv_squeeze", x.device, dy, ctx.wf, None, dx, n, h, w, cout, 3, 1, 1)
         return dx, _wgrad_to(ctx.weight_ref, wg) if ctx.needs_input_grad[1] else None, None
 
 
@@ -676,9 +653,7 @@ class _Conv3x3CatNHWC(torch.autograd.Function):
         x1, x2, weight = ctx.saved_tensors
         if dy is None:
             return None, None, None, None, None
-        dy = dy.contiguous()
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _bf16c(dy)
         dx1 = dx2 = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             dx1, dx2 = torch.empty_like(x1), torch.empty_like(x2)
@@ -709,10 +684,8 @@ class _InstNormLReLUNHWC(torch.autograd.Function):
         b = bias.float().contiguous() if bias is not None else None
         slots = partials if partials is not None and partials.dtype == torch.float64 else None      # slot form; float32: per-tile partials
         tiles = partials if slots is None else None
-        rc = _native.lib().octa_instnorm_lrelu_nhwc_fwd(_native.ctx(x.device.index), _p(x), _p(y), _p(w), _p(b), _p(mean), _p(rstd), B, C, hw, float(slope),
-                                                        float(eps), _p(tiles), int(tiles.shape[1]) if tiles is not None else 0, _p(slots),
-                                                        int(slots.shape[0]) if slots is not None else 0, _native.current_stream_ptr())
-        _native.check(rc, "octa_instnorm_lrelu_nhwc_fwd")
+        _native.launch("octa_instnorm_lrelu_nhwc_fwd", x.device, x, y, w, b, mean, rstd, B, C, hw, float(slope), float(eps),
+                       tiles, int(tiles.shape[1]) if tiles is not None else 0, slots, int(slots.shape[0]) if slots is not None else 0)
         ctx.save_for_backward(x, w, b, mean, rstd)
         ctx.slope, ctx.has_w, ctx.has_b = float(slope), weight is not None, bias is not None
         ctx.w_dtype = weight.dtype if weight is not None else None
@@ -721,9 +694,7 @@ class _InstNormLReLUNHWC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, b, mean, rstd = ctx.saved_tensors
-        dy = dy.contiguous()
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _bf16c(dy)
         B, C = x.shape[0], x.shape[3]
         hw = x.shape[1] * x.shape[2]
         dx = torch.empty_like(x)
@@ -733,10 +704,7 @@ class _InstNormLReLUNHWC(torch.autograd.Function):
         else:
             dw = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_w else None
             db = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_b else None
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        rc = _native.lib().octa_instnorm_lrelu_nhwc_bwd(_native.ctx(x.device.index), p(x), p(dy), p(w), p(b), p(mean), p(rstd), p(dx), p(dw),
-                                                        p(db), B, C, hw, ctx.slope, _native.current_stream_ptr())
-        _native.check(rc, "octa_instnorm_lrelu_nhwc_bwd")
+        _native.launch("octa_instnorm_lrelu_nhwc_bwd", x.device, x, dy, w, b, mean, rstd, dx, dw, db, B, C, hw, ctx.slope)
         return dx, (dw.to(ctx.w_dtype) if dw is not None else None), (db.to(ctx.w_dtype) if db is not None else None), None, None, None
 
 
@@ -778,9 +746,7 @@ class _ConvT2x2NHWC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _bf16c(dy)
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = conv3x3_nhwc(dy, pack_convt2x2(weight)[0], stride=2, tap_mask=0b110110000)
@@ -832,9 +798,7 @@ class _ConvT1x1NHWC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, wm = ctx.saved_tensors
-        dy = dy.contiguous()
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _bf16c(dy)
         n, h, w, cin = x.shape
         cout = dy.shape[3]
         dx = dw = None
@@ -883,8 +847,7 @@ class _Head1NHWC(torch.autograd.Function):
         wv = weight.reshape(-1).float().contiguous()
         y = torch.empty((n, h, w, 1), dtype=torch.bfloat16, device=x.device)
         bv = bias.float().contiguous() if bias is not None else None      # read on the device: no host round trip in the step
-        rc = _native.lib().octa_head1_nhwc_fwd(_native.ctx(x.device.index), _p(x), _p(wv), _p(bv), n * h * w, c, _p(y), _native.current_stream_ptr())
-        _native.check(rc, "octa_head1_nhwc_fwd")
+        _native.launch("octa_head1_nhwc_fwd", x.device, x, wv, bv, n * h * w, c, y)
         ctx.save_for_backward(x, wv)
         ctx.w_shape, ctx.w_dtype, ctx.has_bias = weight.shape, weight.dtype, bias is not None
         return y
@@ -892,15 +855,12 @@ class _Head1NHWC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, wv = ctx.saved_tensors
-        dy = dy.contiguous().to(torch.bfloat16)
+        dy = _bf16c(dy)
         n, h, w, c = x.shape
         dx = torch.empty_like(x)
         dw = torch.empty(c, dtype=torch.float32, device=x.device)
         db = torch.empty(1, dtype=torch.float32, device=x.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
-        rc = _native.lib().octa_head1_nhwc_bwd(_native.ctx(x.device.index), p(x), p(dy), p(wv), n * h * w, c, p(dx), p(dw), p(db),
-                                               _native.current_stream_ptr())
-        _native.check(rc, "octa_head1_nhwc_bwd")
+        _native.launch("octa_head1_nhwc_bwd", x.device, x, dy, wv, n * h * w, c, dx, dw, db)
         return dx, dw.view(ctx.w_shape).to(ctx.w_dtype), (db.to(ctx.w_dtype) if ctx.has_bias else None)
 
 
@@ -921,10 +881,8 @@ class _InstNormLReLUHead1NHWC(torch.autograd.Function):
         mean, rstd = torch.empty(B * C, **f32), torch.empty(B * C, **f32)
         logits = torch.empty((B, H, W, 1), dtype=torch.bfloat16, device=x.device)
         slots = partials if partials is not None and partials.dtype == torch.float64 else None      # statistics of x from the convolution that wrote it
-        rc = _native.lib().octa_instnorm_lrelu_head1_nhwc_fwd(_native.ctx(x.device.index), _p(x), _p(g), _p(bt), _p(hw_), _p(hb), _p(mean), _p(rstd),
-                                                              _p(logits), B, C, H * W, float(slope), float(eps), _p(slots),
-                                                              int(slots.shape[0]) if slots is not None else 0, _native.current_stream_ptr())
-        _native.check(rc, "octa_instnorm_lrelu_head1_nhwc_fwd")
+        _native.launch("octa_instnorm_lrelu_head1_nhwc_fwd", x.device, x, g, bt, hw_, hb, mean, rstd, logits, B, C, H * W, float(slope), float(eps),
+                       slots, int(slots.shape[0]) if slots is not None else 0)
         ctx.save_for_backward(x, g, bt, hw_, mean, rstd)
         ctx.slope = float(slope)
         ctx.meta = (gamma is not None, beta is not None, head_b is not None, head_w.shape, head_w.dtype,
@@ -935,19 +893,14 @@ class _InstNormLReLUHead1NHWC(torch.autograd.Function):
     def backward(ctx, dl):
         x, g, bt, hw_, mean, rstd = ctx.saved_tensors
         has_g, has_b, has_hb, hw_shape, hw_dtype, g_dtype = ctx.meta
-        dl = dl.contiguous()
-        if dl.dtype != torch.bfloat16:
-            dl = dl.to(torch.bfloat16)
+        dl = _bf16c(dl)
         B, H, W, C = x.shape
         f32 = dict(dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x)
         dgb = torch.empty(2 * C, **f32)                   # back to back: one fill clears both
         dg, db = dgb[:C], dgb[C:]
         dhw, dhb = torch.empty(C, **f32), torch.empty(1, **f32)
-        rc = _native.lib().octa_instnorm_lrelu_head1_nhwc_bwd(_native.ctx(x.device.index), _p(x), _p(dl), _p(g), _p(bt), _p(hw_), _p(mean), _p(rstd),
-                                                              _p(dx), _p(dg), _p(db), _p(dhw), _p(dhb), B, C, H * W, ctx.slope,
-                                                              _native.current_stream_ptr())
-        _native.check(rc, "octa_instnorm_lrelu_head1_nhwc_bwd")
+        _native.launch("octa_instnorm_lrelu_head1_nhwc_bwd", x.device, x, dl, g, bt, hw_, mean, rstd, dx, dg, db, dhw, dhb, B, C, H * W, ctx.slope)
         return (dx, dg.to(g_dtype) if has_g else None, db.to(g_dtype) if has_b else None, None, None,
                 dhw.view(hw_shape).to(hw_dtype), dhb.to(hw_dtype) if has_hb else None, None)
 
@@ -997,9 +950,7 @@ class _LazyNorm(torch.autograd.Function):
         mean, rstd, scale, shift = (torch.empty(B * C, **f32) for _ in range(4))
         w = weight.float().contiguous() if weight is not None else None
         b = bias.float().contiguous() if bias is not None else None
-        rc = _native.lib().octa_instnorm_nhwc_stats(_native.ctx(x.device.index), _p(x), _p(w), _p(b), _p(mean), _p(rstd), _p(scale), _p(shift),
-                                                    B, C, hw, float(eps), _native.current_stream_ptr())
-        _native.check(rc, "octa_instnorm_nhwc_stats")
+        _native.launch("octa_instnorm_nhwc_stats", x.device, x, w, b, mean, rstd, scale, shift, B, C, hw, float(eps))
         ctx.save_for_backward(x, w, b, mean, rstd)
         ctx.slope, ctx.has_w, ctx.has_b = float(slope), weight is not None, bias is not None
         ctx.w_dtype = weight.dtype if weight is not None else None
@@ -1025,9 +976,7 @@ class _Materialise(torch.autograd.Function):
         t = t.contiguous()
         y = torch.empty_like(t)
         B, C = t.shape[0], t.shape[3]
-        rc = _native.lib().octa_scale_shift_lrelu_nhwc(_native.ctx(t.device.index), _p(t), _p(y), _p(scale), _p(shift), B, C,
-                                                       t.shape[1] * t.shape[2], float(slope), _native.current_stream_ptr())
-        _native.check(rc, "octa_scale_shift_lrelu_nhwc")
+        _native.launch("octa_scale_shift_lrelu_nhwc", t.device, t, y, scale, shift, B, C, t.shape[1] * t.shape[2], float(slope))
         return y
 
     @staticmethod
@@ -1063,9 +1012,7 @@ class _ConvLazy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x1, sc1, sh1, x2, sc2, sh2, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _bf16c(dy)
         st = ctx.stride
         dx1 = dx2 = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[3]:
@@ -1095,9 +1042,7 @@ def conv4x4_nhwc(x, wt, pad):
     n, h, w, cin = x.shape
     cout = wt.shape[1]
     y = torch.empty((n, h + 2 * pad - 3, w + 2 * pad - 3, cout), dtype=torch.bfloat16, device=x.device)
-    rc = _native.lib().octa_conv4x4_nhwc_fwd(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(wt.data_ptr()),
-                                             ctypes.c_void_p(y.data_ptr()), n, h, w, cin, cout, int(pad), _native.current_stream_ptr())
-    _native.check(rc, "octa_conv4x4_nhwc_fwd")
+    _native.launch("octa_conv4x4_nhwc_fwd", x.device, x, wt, y, n, h, w, cin, cout, int(pad))
     return y
 
 
@@ -1114,9 +1059,7 @@ class _Conv4x4NHWC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _bf16c(dy)
         dx = dw = None
         if ctx.needs_input_grad[0]:
             # dx = full correlation of dy with the flipped kernel, channels transposed: padding 3 - 1 = 2
@@ -1127,9 +1070,7 @@ class _Conv4x4NHWC(torch.autograd.Function):
 
             def wg():
                 d = torch.empty((16, cout, cin), dtype=torch.float32, device=x.device)
-                rc = _native.lib().octa_conv4x4_nhwc_wgrad(_native.ctx(x.device.index), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(dy.data_ptr()),
-                                                           ctypes.c_void_p(d.data_ptr()), n, h, w, cin, cout, _native.current_stream_ptr())
-                _native.check(rc, "octa_conv4x4_nhwc_wgrad")
+                _native.launch("octa_conv4x4_nhwc_wgrad", x.device, x, dy, d, n, h, w, cin, cout)
                 return d.view(4, 4, cout, cin).permute(2, 3, 0, 1).to(weight.dtype)
             dw = _wgrad_to(weight, wg)
         return dx, dw

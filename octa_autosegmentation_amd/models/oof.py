@@ -6,7 +6,6 @@ filters of radii 1..5 and a closed-form 2x2 eigen-analysis per pixel (DESIGN.md 
 (the reference asserts B = 1; here every image of a batch is filtered and normalised on its own). It has no parameters;
 `eval()` / `train()` do nothing. The host helpers below (`radius_constants`, `frequency_grid`, `radial_filter`) restate the
 filter the kernels evaluate; the CPU tests build a float64 torch pipeline from them."""
-import ctypes
 import math
 
 import torch
@@ -60,10 +59,6 @@ def radial_filter(rho: torch.Tensor, r: int) -> torch.Tensor:
     return num / den * a * b
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def _require_cuda(t: torch.Tensor, who: str):
     if not t.is_cuda:
         raise RuntimeError(f"{who} runs on the GPU (no CPU fallback): pass --General.device cuda:0")
@@ -79,10 +74,9 @@ def fft2_c2c_f64(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
     b = xc.shape[0]
     out = torch.empty_like(xc)
     with torch.cuda.device(x.device):
-        lib = _native.lib()
-        ws = torch.empty(max(1, lib.octa_fft2_c2c_f64_workspace_bytes(b, h, w)), dtype=torch.uint8, device=x.device)
-        _native.check(lib.octa_fft2_c2c_f64(_ptr(xc), _ptr(out), b, h, w, int(bool(inverse)), _ptr(ws), _native.current_stream_ptr()),
-                      "octa_fft2_c2c_f64")
+        ws = torch.empty(max(1, _native.lib().octa_fft2_c2c_f64_workspace_bytes(b, h, w)), dtype=torch.uint8, device=x.device)
+        # these entry points take a stream but no context (they bring their workspace along): call(), with the stream as an argument
+        _native.call("octa_fft2_c2c_f64", xc, out, b, h, w, int(bool(inverse)), ws, _native.current_stream_ptr())
     return out.view(x.shape)
 
 
@@ -97,10 +91,8 @@ def _oof_call(img: torch.Tensor, normalize: bool) -> torch.Tensor:
     b = x.shape[0]
     out = torch.empty(x.shape, dtype=torch.float64, device=img.device)
     with torch.cuda.device(img.device):
-        lib = _native.lib()
-        ws = torch.empty(max(1, lib.octa_oof_workspace_bytes(b, h, w)), dtype=torch.uint8, device=img.device)
-        fn, name = (lib.octa_oof_2d, "octa_oof_2d") if normalize else (lib.octa_oof_2d_response, "octa_oof_2d_response")
-        _native.check(fn(_ptr(x), _ptr(out), b, h, w, _ptr(ws), _native.current_stream_ptr()), name)
+        ws = torch.empty(max(1, _native.lib().octa_oof_workspace_bytes(b, h, w)), dtype=torch.uint8, device=img.device)
+        _native.call("octa_oof_2d" if normalize else "octa_oof_2d_response", x, out, b, h, w, ws, _native.current_stream_ptr())
     return out.view(img.shape)
 
 

@@ -1,8 +1,6 @@
 """Inference post-processing on the GPU: the `post_processing.prediction` list of the configs
 (configs/config_ves_seg-S.yml:103-113: Activations(sigmoid) -> AsDiscrete(0.5) -> RemoveSmallObjects(160), label:
 CastToType uint8) as used by test.py / validate.py, for a whole batch of logits in HBM."""
-import ctypes
-
 import torch
 
 from .. import _native
@@ -15,10 +13,7 @@ def remove_small_objects_device(mask, min_size=64, connectivity=1, on_value=1):
     shape = mask.shape
     m = mask.reshape(-1, shape[-2], shape[-1]).to(torch.uint8).contiguous()
     out = torch.empty_like(m)
-    rc = _native.lib().octa_remove_small_objects(_native.ctx(m.device.index), ctypes.c_void_p(m.data_ptr()), m.shape[0], m.shape[1], m.shape[2],
-                                                 int(min_size), int(connectivity), int(on_value), ctypes.c_void_p(out.data_ptr()),
-                                                 _native.current_stream_ptr())
-    _native.check(rc, "octa_remove_small_objects")
+    _native.launch("octa_remove_small_objects", m.device, m, m.shape[0], m.shape[1], m.shape[2], int(min_size), int(connectivity), int(on_value), out)
     return out.view(shape)
 
 

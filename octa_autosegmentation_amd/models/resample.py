@@ -4,8 +4,6 @@ Reference: models/networks.py:244-262 (Upsample), :264-289 (Downsample), nn.Refl
 ResnetGenerator (:366-368, :404-421). Every op is one kernel per direction; tensors may be NCHW (``layout="nchw"``) or
 NHWC (``layout="nhwc"``), float32 or bfloat16. There is no torch fallback on a GPU tensor: a missing extension raises.
 """
-import ctypes
-
 import torch
 
 from .. import _native
@@ -36,12 +34,7 @@ def _planes(shape, layout):
 
 def _launch(name, src, dst, b, h, w, c, pad):
     dtype = {torch.float32: 0, torch.bfloat16: 1}[src.dtype]
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    args = [_native.ctx(src.device.index), p(src), p(dst), dtype, b, h, w, c]
-    if pad is not None:
-        args.append(pad)
-    rc = getattr(_native.lib(), name)(*args, _native.current_stream_ptr())
-    _native.check(rc, name)
+    _native.launch(name, src.device, src, dst, dtype, b, h, w, c, *(() if pad is None else (pad,)))
 
 
 class _Resample(torch.autograd.Function):

@@ -9,15 +9,9 @@ The library has three kernels (include/octa_hip.h): expand (1 -> C), squeeze (C 
 (g[c][t] = sum_q a[q][c] s[q + t - pad], a wide, s one channel). With one input channel: forward = expand, dx = squeeze of dy, dw =
 wgrad(a = dy, s = x). With one output channel: forward = squeeze, dx = expand of dy, and substituting q = p + t - pad in dw[t][c] =
 sum_p dy[p] x[p + t - pad][c] gives sum_q x[q][c] dy[q + t' - pad'] with t' the flipped tap: wgrad(a = x, s = dy, flip, pad')."""
-import ctypes
-
 import torch
 
 from .. import _native
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _w2d(weight):
@@ -30,27 +24,23 @@ def _expand(s, w2d, bias, k, pad, flip, slope):
     n, hs, ws = s.shape
     c = w2d.shape[0]
     out = torch.empty((n, hs + 2 * pad - k + 1, ws + 2 * pad - k + 1, c), dtype=torch.bfloat16, device=s.device)
-    _native.check(_native.lib().octa_thinconv_expand(_native.ctx(s.device.index), _ptr(s), _ptr(w2d), _ptr(bias), _ptr(out), n, hs, ws, c, k, pad,
-                                                     int(flip), float(slope), _native.current_stream_ptr()), "octa_thinconv_expand")
+    _native.launch("octa_thinconv_expand", s.device, s, w2d, bias, out, n, hs, ws, c, k, pad, int(flip), float(slope))
     return out
 
 
 def _squeeze(a, w2d, bias, k, pad, flip):
     n, ha, wa, c = a.shape
     out = torch.empty((n, ha + 2 * pad - k + 1, wa + 2 * pad - k + 1), dtype=torch.bfloat16, device=a.device)
-    _native.check(_native.lib().octa_thinconv_squeeze(_native.ctx(a.device.index), _ptr(a), _ptr(w2d), _ptr(bias), _ptr(out), n, ha, wa, c, k, pad,
-                                                      int(flip), _native.current_stream_ptr()), "octa_thinconv_squeeze")
+    _native.launch("octa_thinconv_squeeze", a.device, a, w2d, bias, out, n, ha, wa, c, k, pad, int(flip))
     return out
 
 
 def _wgrad(a, s, k, pad, flip, want_asum):
     n, ha, wa, c = a.shape
-    lib = _native.lib()
-    scratch = torch.empty(int(lib.octa_thinconv_wgrad_scratch_floats(n, ha, c, k)), dtype=torch.float32, device=a.device)
+    scratch = torch.empty(int(_native.lib().octa_thinconv_wgrad_scratch_floats(n, ha, c, k)), dtype=torch.float32, device=a.device)
     g = torch.empty((c, k * k), dtype=torch.float32, device=a.device)
     asum = torch.empty(c, dtype=torch.float32, device=a.device) if want_asum else None
-    _native.check(lib.octa_thinconv_wgrad(_native.ctx(a.device.index), _ptr(a), _ptr(s), _ptr(scratch), _ptr(g), _ptr(asum), n, ha, wa, s.shape[1],
-                                          s.shape[2], c, k, pad, int(flip), _native.current_stream_ptr()), "octa_thinconv_wgrad")
+    _native.launch("octa_thinconv_wgrad", a.device, a, s, scratch, g, asum, n, ha, wa, s.shape[1], s.shape[2], c, k, pad, int(flip))
     return g, asum
 
 
@@ -77,8 +67,7 @@ class _ConvFrom1(torch.autograd.Function):
         dy = _bf16c(dy)
         if slope != 1.0:                                   # LeakyReLU': the sign of the output is the sign of its input (slope > 0)
             g = torch.empty_like(dy)                       # one launch instead of torch's compare, scale and select (same values: y > 0 ? dy : bf16(dy * slope))
-            _native.check(_native.lib().octa_lrelu_bwd_bf16(_native.ctx(dy.device.index), _ptr(y), _ptr(dy), _ptr(g), dy.numel(), float(slope),
-                                                           _native.current_stream_ptr()), "octa_lrelu_bwd_bf16")
+            _native.launch("octa_lrelu_bwd_bf16", dy.device, y, dy, g, dy.numel(), float(slope))
             dy = g
         dx = _squeeze(dy, _w2d(weight), None, k, k - 1 - pad, True).to(x_dtype) if ctx.needs_input_grad[0] else None
         dw = db = None

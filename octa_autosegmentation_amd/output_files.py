@@ -82,13 +82,11 @@ class SampleFileWriter:
         threads = self.threads
 
         def job(keep=(e, off, img, lab, dirs_c, names_c, cfg)):        # the arrays stay alive until the call has returned
-            p = lambda a: ctypes.c_void_p(a.ctypes.data) if a is not None else None
-            rc = _native.lib().octa_write_sample_files(
-                B, ctypes.cast(dirs_c, ctypes.c_void_p), ctypes.cast(names_c, ctypes.c_void_p), p(e), p(off), p(img), int(img.shape[2]) if img is not None else 0,
-                int(img.shape[1]) if img is not None else 0, p(lab), lab_w,
-                int(lab.shape[1]) if lab is not None else 0, 1 if packed else 0, cfg, len(cfg) if cfg is not None else 0, -1, int(threads))
+            host = lambda a: a.ctypes.data if a is not None else None        # numpy arrays: the address is spelled out
             try:
-                _native.check(rc, "octa_write_sample_files")
+                _native.call("octa_write_sample_files", B, ctypes.cast(dirs_c, ctypes.c_void_p), ctypes.cast(names_c, ctypes.c_void_p), host(e), host(off),
+                             host(img), int(img.shape[2]) if img is not None else 0, int(img.shape[1]) if img is not None else 0, host(lab), lab_w,
+                             int(lab.shape[1]) if lab is not None else 0, 1 if packed else 0, cfg, len(cfg) if cfg is not None else 0, -1, int(threads))
             finally:
                 if on_done is not None:
                     on_done()

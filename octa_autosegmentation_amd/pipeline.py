@@ -10,7 +10,6 @@ Mirrors what the reference produces with
   * label : all edges, positions as read back from the CSV text, rasterised at 1216x1216 and
             Floyd-Steinberg binarised (visualize_vessel_graphs.py:95-99).
 """
-import ctypes
 
 import numpy as np
 
@@ -275,8 +274,7 @@ class TripleGenerator:
         gate_out = None
         if successor:
             gate_out = torch.zeros(3, dtype=torch.int32, device=self.device)        # what the gate kernel saw: 1 resident / 2 timed out, ticks waited, workgroups signed in
-            _native.check(_native.lib().octa_order_wait_launch(_native.ctx(self.device.index), ticket + 1, gate.timeout_us, gate.settle_us,
-                                                               ctypes.c_void_p(gate_out.data_ptr()), _native.current_stream_ptr()), "octa_order_wait_launch")
+            _native.launch("octa_order_wait_launch", self.device, ticket + 1, gate.timeout_us, gate.settle_us, gate_out)
             t1 = time.time()
             out = self._render(res, want_label, plans)
         out["wall"] = {"t1": t1, "render_enqueue_s": time.time() - t1, "ordered_behind_successor": bool(successor), "gate": gate_out, "ticket": int(ticket)}

@@ -87,9 +87,7 @@ def skeletonize_device(mask, return_passes=False):
     passes = ctypes.c_int(0)
     if m.numel():
         with torch.cuda.device(m.device):
-            rc = _native.lib().octa_skeletonize(_native.ctx(m.device.index), ctypes.c_void_p(m.data_ptr()), m.shape[0], m.shape[1], m.shape[2],
-                                                ctypes.c_void_p(out.data_ptr()), ctypes.byref(passes), _native.current_stream_ptr())
-        _native.check(rc, "octa_skeletonize")
+            _native.launch("octa_skeletonize", m.device, m, m.shape[0], m.shape[1], m.shape[2], out, ctypes.byref(passes))
     out = out.view(shape)
     return (out, passes.value) if return_passes else out
 

@@ -32,7 +32,7 @@ def _save_strip(path, images):
         cols.append(a)
         cols.append(np.full((h, 4), 128, np.uint8))
     strip = np.ascontiguousarray(np.concatenate(cols[:-1], axis=1))
-    _native.check(_native.lib().octa_png_write_gray8(path.encode(), strip.ctypes.data, strip.shape[1], strip.shape[0], -1), "octa_png_write_gray8")
+    _native.call("octa_png_write_gray8", path.encode(), strip.ctypes.data, strip.shape[1], strip.shape[0], -1)
     return path
 
 
@@ -43,7 +43,7 @@ def plot_single_image(save_dir: str, input: torch.Tensor, name: str = None):
     if a.ndim != 2:
         raise NotImplementedError("3-D predictions (nifti) are outside the MI355X hot path")
     path = os.path.join(save_dir, ".".join(name.split(".")[:-1]) + ".png")
-    _native.check(_native.lib().octa_png_write_gray8(path.encode(), a.ctypes.data, a.shape[1], a.shape[0], -1), "octa_png_write_gray8")
+    _native.call("octa_png_write_gray8", path.encode(), a.ctypes.data, a.shape[1], a.shape[0], -1)
     return path
 
 

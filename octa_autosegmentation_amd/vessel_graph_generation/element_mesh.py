@@ -130,7 +130,7 @@ class KD_Tree(SpacePartitioner, Generic[T]):
                 if n > _KD_CAP:
                     raise ValueError(f"KD_Tree: the device order takes at most {_KD_CAP} points, got {n}")
                 idx = np.zeros(n, np.int32)
-                _native.check(_native.lib().octa_sim_kat_kd_order(_native.ctx(), pts.ctypes.data, n, None, idx.ctypes.data), "octa_sim_kat_kd_order")
+                _native.call("octa_sim_kat_kd_order", _native.ctx(), pts.ctypes.data, n, None, idx.ctypes.data)
                 rank = np.empty(n, np.int64)
                 rank[idx] = np.arange(n)
                 self._rank = rank

@@ -293,7 +293,7 @@ class BatchSimulator:
         h = ctypes.c_void_p()
         # the build is an ARGUMENT (round 3 set the process-wide OCTA_SIM_BUILD around the call: another generator thread creating a
         # simulator in that window got the wide-field build too, and setenv raced with the library's getenv)
-        _native.check(self._lib.octa_sim_create_ex(self._ctx, ctypes.byref(self._cfg), self.batch, 2 if force_large else 0, ctypes.byref(h)), "octa_sim_create")
+        _native.call("octa_sim_create_ex", self._ctx, ctypes.byref(self._cfg), self.batch, 2 if force_large else 0, ctypes.byref(h))
         self._h = h
         self.is_large = bool(self._lib.octa_sim_is_large(h))      # bound to the wide-field build
 
@@ -319,7 +319,7 @@ class BatchSimulator:
         rc = call()
         if rc == -3 and not self.is_large and os.environ.get("OCTA_SIM_BUILD") != "default":
             stats = np.zeros((self.batch, 32), np.int64)
-            _native.check(self._lib.octa_sim_stats(self._h, stats.ctypes.data), "octa_sim_stats")
+            _native.call("octa_sim_stats", self._h, stats.ctypes.data)
             bits = int(np.bitwise_or.reduce(stats[:, 0]))
             CAPACITY = 1 | 2 | 4 | 8 | 16 | 32 | 64 | 256 | 512       # node, O2, CO2, group, pair, set, uniform-stream, request, accepted-sink capacities
             if bits and not (bits & ~CAPACITY):
@@ -344,27 +344,26 @@ class BatchSimulator:
     def _collect(self):
         off = np.zeros(self.batch + 1, np.int64)
         n_art = np.zeros(self.batch, np.int64)
-        _native.check(self._lib.octa_sim_edge_offsets(self._h, off.ctypes.data, n_art.ctypes.data), "octa_sim_edge_offsets")
+        _native.call("octa_sim_edge_offsets", self._h, off.ctypes.data, n_art.ctypes.data)
         edges = d_edges = None
         if self.device_export:
             # the edge list is written by a kernel on the stream of the run and stays in HBM (the rasteriser reads it there); the host
             # copy is made when somebody asks for `.edges`
             import torch
             d_edges = torch.empty((int(off[-1]), 7), dtype=torch.float64, device=torch.device("cuda", self.device_index))
-            _native.check(self._lib.octa_sim_export_edges_device(self._h, ctypes.c_void_p(d_edges.data_ptr()), _native.current_stream_ptr()),
-                          "octa_sim_export_edges_device")
+            _native.call("octa_sim_export_edges_device", self._h, d_edges, _native.current_stream_ptr())
         else:
             edges = np.zeros((int(off[-1]), 7))
-            _native.check(self._lib.octa_sim_export_edges(self._h, edges.ctypes.data), "octa_sim_export_edges")
+            _native.call("octa_sim_export_edges", self._h, edges.ctypes.data)
         stats = np.zeros((self.batch, 32), np.int64)
-        _native.check(self._lib.octa_sim_stats(self._h, stats.ctypes.data), "octa_sim_stats")
+        _native.call("octa_sim_stats", self._h, stats.ctypes.data)
         timing = np.zeros(8)
-        _native.check(self._lib.octa_sim_timing(self._h, timing.ctypes.data), "octa_sim_timing")
+        _native.call("octa_sim_timing", self._h, timing.ctypes.data)
         svc = np.zeros(5)
-        _native.check(self._lib.octa_sim_service_stats(self._h, svc.ctypes.data), "octa_sim_service_stats")
+        _native.call("octa_sim_service_stats", self._h, svc.ctypes.data)
         res = SimulationResult(edges, off, n_art, stats, d_edges)
         res.spans = np.zeros((self.batch, 2), np.int64)      # 100 MHz device clock: first taken / last left by a workgroup
-        _native.check(self._lib.octa_sim_spans(self._h, res.spans.ctypes.data), "octa_sim_spans")
+        _native.call("octa_sim_spans", self._h, res.spans.ctypes.data)
         res.service = dict(tickets=int(svc[0]), max_absence_ms=svc[1], relaunches=int(svc[2]), parked=int(svc[3]), max_callback_ms=svc[4])
         res.timing = dict(kernel_a_ms=timing[0], launches_a=int(timing[1]), kernel_b_ms=timing[2], launches_b=int(timing[3]),
                           loop_wall_ms=timing[4], host_bif_ms=timing[5], bif_requests=int(timing[6]), hbm_bytes=int(timing[7]))
@@ -376,15 +375,14 @@ class BatchSimulator:
         n_iter = sum(int(m["I"]) for m in self._config["Greenhouse"]["modes"] if int(m["I"]) > 0)
         out = np.zeros((self.batch, n_iter, 4), np.int32)
         if n_iter:
-            _native.check(self._lib.octa_sim_trace(self._h, out.ctypes.data), "octa_sim_trace")
+            _native.call("octa_sim_trace", self._h, out.ctypes.data)
         return out
 
     def fields(self, k):
         cap = 1 << 18 if self.is_large else 16384
         oxy, co2 = np.zeros((cap, 3)), np.zeros((cap, 3))
         no, nc = ctypes.c_int64(), ctypes.c_int64()
-        _native.check(self._lib.octa_sim_fields(self._h, int(k), oxy.ctypes.data, len(oxy), ctypes.byref(no),
-                                                co2.ctypes.data, len(co2), ctypes.byref(nc)), "octa_sim_fields")
+        _native.call("octa_sim_fields", self._h, int(k), oxy.ctypes.data, len(oxy), ctypes.byref(no), co2.ctypes.data, len(co2), ctypes.byref(nc))
         return oxy[: no.value].copy(), co2[: nc.value].copy()
 
 
@@ -406,7 +404,7 @@ class BatchSimulator:
     def np_state(self, k):
         """numpy's MT19937 state of sample k after the run: 624 words + position."""
         out = np.zeros(625, np.uint32)
-        _native.check(self._lib.octa_sim_np_state(self._h, int(k), out.ctypes.data), "octa_sim_np_state")
+        _native.call("octa_sim_np_state", self._h, int(k), out.ctypes.data)
         return out
 
 

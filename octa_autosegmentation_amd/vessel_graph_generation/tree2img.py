@@ -9,7 +9,6 @@ backend draws for the reference. There is no CPU path here.
 from random import random
 from typing import Sequence, Tuple
 
-import ctypes
 import numpy as np
 
 from .. import _native
@@ -70,12 +69,9 @@ def rasterize_edges_device_plan(d_edges, edge_off, image_resolution, MIP_axis=2,
         raise ValueError("d_edges must be a contiguous float64 CUDA tensor")
     if d_edges.numel() != int(edge_off[-1]) * 7:
         raise ValueError("edge_off[-1] does not match the number of edges")
-    h = _native.ctx(d_edges.device.index)
-    rc = _native.lib().octa_rasterize_2d_plan(
-        h, B, ctypes.c_void_p(d_edges.data_ptr()), ctypes.c_void_p(edge_off.ctypes.data),
-        ctypes.c_void_p(d_keep.data_ptr()) if d_keep is not None else None,
-        no_pixels_x, no_pixels_y, int(MIP_axis), float(min_radius), float(max_radius), _native.current_stream_ptr())
-    _native.check(rc, "octa_rasterize_2d_plan")
+    h = _native.ctx(d_edges.device.index)          # kept in the token: the draw half must find this context's plan
+    _native.launch("octa_rasterize_2d_plan", d_edges.device, B, d_edges, edge_off.ctypes.data, d_keep, no_pixels_x, no_pixels_y, int(MIP_axis),
+                   float(min_radius), float(max_radius), ctx=h)
     return dict(ctx=h, shape=(B, no_pixels_y, no_pixels_x), device=d_edges.device)
 
 
@@ -86,8 +82,7 @@ def rasterize_edges_device_draw(plan, out=None):
     if out is None:
         out = torch.empty(plan["shape"], dtype=torch.uint8, device=plan["device"])
     if plan["shape"][0] > 0:
-        rc = _native.lib().octa_rasterize_2d_draw(plan["ctx"], ctypes.c_void_p(out.data_ptr()), _native.current_stream_ptr())
-        _native.check(rc, "octa_rasterize_2d_draw")
+        _native.launch("octa_rasterize_2d_draw", plan["device"], out, ctx=plan["ctx"])
     return out
 
 
@@ -169,13 +164,8 @@ def voxelize_edges_device(d_edges, edge_off, volume_dimensions, min_radius=-np.i
     if d_edges.dtype != torch.float64 or not d_edges.is_cuda or not d_edges.is_contiguous():
         raise ValueError("d_edges must be a contiguous float64 CUDA tensor")
     out = torch.empty((B, int(pd[0]), int(pd[1]), int(pd[2])), dtype=torch.int16, device=d_edges.device)
-    h = _native.ctx(d_edges.device.index)
-    rc = _native.lib().octa_voxelize_3d(
-        h, B, ctypes.c_void_p(d_edges.data_ptr()), ctypes.c_void_p(edge_off.ctypes.data),
-        ctypes.c_void_p(d_keep.data_ptr()) if d_keep is not None else None, ctypes.c_void_p(dims.ctypes.data),
-        float(min_radius), float(max_radius), int(bool(ignore_z)), ctypes.c_void_p(out.data_ptr()),
-        _native.current_stream_ptr())
-    _native.check(rc, "octa_voxelize_3d")
+    _native.launch("octa_voxelize_3d", d_edges.device, B, d_edges, edge_off.ctypes.data, d_keep, dims.ctypes.data, float(min_radius), float(max_radius),
+                   int(bool(ignore_z)), out)
     return out
 
 
@@ -200,10 +190,7 @@ def binarize_label_device(d_img):
         raise ValueError("d_img must be a contiguous uint8 CUDA tensor [B,H,W]")
     B, H, W = d_img.shape
     out = torch.empty_like(d_img)
-    h = _native.ctx(d_img.device.index)
-    rc = _native.lib().octa_fs_dither(h, B, ctypes.c_void_p(d_img.data_ptr()), W, H,
-                                      ctypes.c_void_p(out.data_ptr()), _native.current_stream_ptr())
-    _native.check(rc, "octa_fs_dither")
+    _native.launch("octa_fs_dither", d_img.device, B, d_img, W, H, out)
     return out
 
 
@@ -216,9 +203,7 @@ def pack_label_bits_device(d_bits, out=None):
     B, H, W = d_bits.shape
     if out is None:
         out = torch.empty((B, H, (W + 7) // 8), dtype=torch.uint8, device=d_bits.device)
-    rc = _native.lib().octa_pack_bits(_native.ctx(d_bits.device.index), ctypes.c_void_p(d_bits.data_ptr()), ctypes.c_void_p(out.data_ptr()), B * H, W,
-                                      _native.current_stream_ptr())
-    _native.check(rc, "octa_pack_bits")
+    _native.launch("octa_pack_bits", d_bits.device, d_bits, out, B * H, W)
     return out
 
 
@@ -229,10 +214,7 @@ def maximum_u8_device(a, b):
         raise ValueError("inputs must be uint8 tensors of equal shape")
     a, b = a.contiguous(), b.contiguous()
     out = torch.empty_like(a)
-    h = _native.ctx(a.device.index)
-    rc = _native.lib().octa_max_u8(h, ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()),
-                                   ctypes.c_void_p(out.data_ptr()), a.numel(), _native.current_stream_ptr())
-    _native.check(rc, "octa_max_u8")
+    _native.launch("octa_max_u8", a.device, a, b, out, a.numel())
     return out
 
 
@@ -242,11 +224,10 @@ def save_2d_img(img: np.ndarray, out_dir: str, name: str):
     a = np.ascontiguousarray(img.astype(np.uint8))
     if a.ndim != 2:
         raise ValueError("save_2d_img expects a 2-D image")
-    _native.check(_native.lib().octa_png_write_gray8(f'{out_dir}/{name}.png'.encode(), a.ctypes.data, a.shape[1], a.shape[0], -1),
-                  "octa_png_write_gray8")
+    _native.call("octa_png_write_gray8", f'{out_dir}/{name}.png'.encode(), a.ctypes.data, a.shape[1], a.shape[0], -1)
 
 
 def save_label_png(bits: np.ndarray, path: str):
     """visualize_vessel_graphs.py:99: a mode "1" PNG (non-zero = white) from a binarised label."""
     a = np.ascontiguousarray(bits.astype(np.uint8))
-    _native.check(_native.lib().octa_png_write_bits(str(path).encode(), a.ctypes.data, a.shape[1], a.shape[0], -1), "octa_png_write_bits")
+    _native.call("octa_png_write_bits", str(path).encode(), a.ctypes.data, a.shape[1], a.shape[0], -1)
