@@ -714,6 +714,11 @@ int octa_sim_stats(octa_sim *sim, int64_t *h_stats);
  * the same for every order of the cKDTree query results (no kd order built), conversions that built the kd order. */
 int octa_sim_kd_paths(octa_sim *sim, int64_t *h_paths);
 
+/* How the assignments of the last run found each attractor's nearest active node, h_paths[B][2] int64, summed over the iterations and
+ * both forests: attractors answered from the forest's previous assignment and the nodes created since, attractors answered by the
+ * grid scan. */
+int octa_sim_assign_paths(octa_sim *sim, int64_t *h_paths);
+
 /* When each sample held a CU (persistent form): h_spans[B][2] = the GPU's 100 MHz wall clock when a workgroup first took the sample
  * and when it last left it. The clock is common to all launches on the device, so spans of concurrent launches can be laid over
  * each other: sum of spans / (CUs x window) = the share of CU time the simulator used (bench.py's cu_time_used). */

@@ -91,6 +91,7 @@ SIGNATURES = {
     "octa_sim_trace": (c_int, [c_void_p, c_void_p]),
     "octa_sim_stats": (c_int, [c_void_p, c_void_p]),
     "octa_sim_kd_paths": (c_int, [c_void_p, c_void_p]),
+    "octa_sim_assign_paths": (c_int, [c_void_p, c_void_p]),
     "octa_sim_timing": (c_int, [c_void_p, c_void_p]),
     "octa_sim_service_stats": (c_int, [c_void_p, c_void_p]),
     "octa_sim_geometry": (c_int, [c_int, c_void_p]),

@@ -46,6 +46,7 @@ using namespace OCTA_SIMK;
 #define octa_sim_trace OCTA_SIM_FN(trace)
 #define octa_sim_stats OCTA_SIM_FN(stats)
 #define octa_sim_kd_paths OCTA_SIM_FN(kd_paths)
+#define octa_sim_assign_paths OCTA_SIM_FN(assign_paths)
 #define octa_sim_fields OCTA_SIM_FN(fields)
 #define octa_sim_service_stats OCTA_SIM_FN(service_stats)
 #define octa_sim_geometry OCTA_SIM_FN(geometry)
@@ -81,6 +82,8 @@ struct BatchPtrs {
     double *oxy, *co2, *cand, *py_u;
     unsigned *py_state;   // [B][625] CPython generator states behind the stump draws (input of py_uniform_kernel)
     int *nn, *act_list;
+    int *nn_prev[2];      // [B][OCAP] per forest: phase_assign's winners of the previous assignment and their squared distances (sim_core.h)
+    double *nn_d2[2];
     unsigned *sorted;
     int *gnode, *gstart, *gcount;
     Rec *rec;
@@ -126,6 +129,8 @@ __device__ __forceinline__ SimArrays sample_arrays(const BatchPtrs &B, int s) {
         A.nch1[f] = B.nch1[f] + (size_t)s * NCAP;
         A.nnch[f] = B.nnch[f] + (size_t)s * NCAP;
         A.nact[f] = B.nact[f] + (size_t)s * NCAP;
+        A.nn_prev[f] = B.nn_prev[f] + (size_t)s * OCAP;
+        A.nn_d2[f] = B.nn_d2[f] + (size_t)s * OCAP;
     }
     A.oxy = B.oxy + (size_t)s * OCAP * 3;
     A.co2 = B.co2 + (size_t)s * CCAP * 3;
@@ -824,6 +829,7 @@ extern "C" int octa_sim_create(octa_ctx *ctx, const octa_sim_config *c, int B, O
         rc |= dev_alloc(S, &P.npos[f], nb * NCAP * 3); rc |= dev_alloc(S, &P.nrad[f], nb * NCAP); rc |= dev_alloc(S, &P.nkap[f], nb * NCAP);
         rc |= dev_alloc(S, &P.npar[f], nb * NCAP); rc |= dev_alloc(S, &P.nch0[f], nb * NCAP); rc |= dev_alloc(S, &P.nch1[f], nb * NCAP);
         rc |= dev_alloc(S, &P.nnch[f], nb * NCAP); rc |= dev_alloc(S, &P.nact[f], nb * NCAP);
+        rc |= dev_alloc(S, &P.nn_prev[f], nb * OCAP); rc |= dev_alloc(S, &P.nn_d2[f], nb * OCAP);
     }
     rc |= dev_alloc(S, &P.oxy, nb * OCAP * 3); rc |= dev_alloc(S, &P.co2, nb * CCAP * 3);
     rc |= dev_alloc(S, &P.cand, nb * NCANDCAP * 3); rc |= dev_alloc(S, &P.py_u, nb * PYCAP); rc |= dev_alloc(S, &P.py_state, nb * 625);
@@ -1400,6 +1406,12 @@ extern "C" int octa_sim_stats(OCTA_SIM_T *S, int64_t *h_stats) {
 extern "C" int octa_sim_kd_paths(OCTA_SIM_T *S, int64_t *h_paths) {
     if (!S || !S->ran || !h_paths) { octa::set_error("octa_sim_kd_paths: run the simulation first"); return -2; }
     for (int s = 0; s < S->B; s++) { h_paths[2 * s] = S->h_sc[s].kd_path[0]; h_paths[2 * s + 1] = S->h_sc[s].kd_path[1]; }
+    return 0;
+}
+
+extern "C" int octa_sim_assign_paths(OCTA_SIM_T *S, int64_t *h_paths) {
+    if (!S || !S->ran || !h_paths) { octa::set_error("octa_sim_assign_paths: run the simulation first"); return -2; }
+    for (int s = 0; s < S->B; s++) { h_paths[2 * s] = S->h_sc[s].assign_path[0]; h_paths[2 * s + 1] = S->h_sc[s].assign_path[1]; }
     return 0;
 }
 

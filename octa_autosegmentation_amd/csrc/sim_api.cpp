@@ -27,6 +27,7 @@ struct octa_simL_impl;
     int octa_sim##SFX##_trace(T *, int32_t *);                                                                                                  \
     int octa_sim##SFX##_stats(T *, int64_t *);                                                                                                  \
     int octa_sim##SFX##_kd_paths(T *, int64_t *);                                                                                               \
+    int octa_sim##SFX##_assign_paths(T *, int64_t *);                                                                                           \
     int octa_sim##SFX##_spans(T *, int64_t *);                                                                                                  \
     int octa_sim##SFX##_timing(T *, double *);                                                                                                  \
     int octa_sim##SFX##_service_stats(T *, double *);                                                                                           \
@@ -125,6 +126,7 @@ extern "C" int octa_sim_export_edges_device(octa_sim *sim, double *e, void *st) 
 extern "C" int octa_sim_trace(octa_sim *sim, int32_t *t) { NEED(sim, "octa_sim_trace") return FWD(octa_simS_trace(sim->s, t), octa_simL_trace(sim->l, t)); }
 extern "C" int octa_sim_stats(octa_sim *sim, int64_t *t) { NEED(sim, "octa_sim_stats") return FWD(octa_simS_stats(sim->s, t), octa_simL_stats(sim->l, t)); }
 extern "C" int octa_sim_kd_paths(octa_sim *sim, int64_t *t) { NEED(sim, "octa_sim_kd_paths") return FWD(octa_simS_kd_paths(sim->s, t), octa_simL_kd_paths(sim->l, t)); }
+extern "C" int octa_sim_assign_paths(octa_sim *sim, int64_t *t) { NEED(sim, "octa_sim_assign_paths") return FWD(octa_simS_assign_paths(sim->s, t), octa_simL_assign_paths(sim->l, t)); }
 extern "C" int octa_sim_spans(octa_sim *sim, int64_t *t) { NEED(sim, "octa_sim_spans") return FWD(octa_simS_spans(sim->s, t), octa_simL_spans(sim->l, t)); }
 extern "C" int octa_sim_timing(octa_sim *sim, double *t) { NEED(sim, "octa_sim_timing") return FWD(octa_simS_timing(sim->s, t), octa_simL_timing(sim->l, t)); }
 extern "C" int octa_sim_service_stats(octa_sim *sim, double *t) { NEED(sim, "octa_sim_service_stats") return FWD(octa_simS_service_stats(sim->s, t), octa_simL_service_stats(sim->l, t)); }

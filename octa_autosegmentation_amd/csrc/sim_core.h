@@ -168,6 +168,11 @@ struct SampleScalars {
     int parked, finished;
     long t_begin, t_end;           // 100 MHz wall clock when a workgroup first took the sample / last left it
     int fl_pending[2];             // marked nodes of forest f whose Murray radii are still to be evaluated from A.fl_rec (deferred flush, round 6)
+    // phase_assign's memory of forest f's previous assignment (SimArrays::nn_prev / nn_d2): the entries of the attractors [0, n_cached)
+    // are valid -- nearest active node among the nodes [0, n_nodes_cached) within delta_cached. All zero: no memory (a fresh sample).
+    int n_cached[2], n_nodes_cached[2];
+    double delta_cached[2];
+    long assign_path[2];           // attractor queries answered from that memory / by the grid scan (sum over both forests)
 };
 
 // pointers to ONE sample's slices
@@ -194,6 +199,13 @@ struct SimArrays {
     const double *py_u;  // [PYCAP]
     // scratch
     int *nn;             // [OCAP] nearest active node per attractor
+    // phase_assign's result of the forest's PREVIOUS assignment, kept from iteration to iteration and moved along by the compactions of
+    // the attractor lists: the winner (-1: no active node within that assignment's delta) and its exact squared distance. The host
+    // harness may leave them unset (null): its phase_assign then answers every attractor by the grid scan.
+    int *nn_prev[2] = {nullptr, nullptr};     // [OCAP]
+    double *nn_d2[2] = {nullptr, nullptr};    // [OCAP]
+    OCTA_HD int *nn_prev_of(int f) const { return f ? nn_prev[1] : nn_prev[0]; }
+    OCTA_HD double *nn_d2_of(int f) const { return f ? nn_d2[1] : nn_d2[0]; }
     int *act_list;       // [NCAP]
     unsigned *sorted;    // [SORTCAP] attractors grouped by their nearest node (groups in dict order, members ascending)
     int *gnode, *gstart, *gcount;  // [GCAP]
@@ -225,6 +237,10 @@ struct SimArrays {
 // of register spills). Used for values that come out of the LDS or out of registers. (Round 3 blamed the irreproducible 512-sample
 // batches it saw with uniform annotations on scalar loads of the sample's counters; round 4 found no scalar load of mutable data in the
 // ISA and traced the events to a barrier without its LDS wait, see octa_block_sync below.)
+// Keeps the compiler from moving memory accesses across this point: a group of independent loads written in front of it is ISSUED in
+// front of it, whatever the register pressure says (the persistent kernel is at its 256 registers, and the scheduler otherwise sinks
+// every load to its first use -- one dependent round trip per element instead of one per group).
+#define OCTA_ISSUE_LOADS() asm volatile("" ::: "memory")
 #if defined(__HIP_DEVICE_COMPILE__)
 #define OCTA_UNI(x) __builtin_amdgcn_readfirstlane(x)
 #else
@@ -405,6 +421,13 @@ OCTA_HD inline int atomic_add_int(int *p, int v) {
     return atomicAdd(p, v);
 #else
     int o = *p; *p = o + v; return o;
+#endif
+}
+OCTA_HD inline int atomic_xchg_int(int *p, int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return atomicExch(p, v);
+#else
+    int o = *p; *p = v; return o;
 #endif
 }
 OCTA_HD inline void atomic_or_int(int *p, int v) {
@@ -2340,6 +2363,15 @@ OCTA_HD inline void phase_sample(const Blk &b, const SimArrays &A, const SimCons
 }
 
 // ------------------------------------------------------------------ phase: nearest active node + dict order
+constexpr int ASSIGN_STAGE = 256;      // nodes created since the forest's previous assignment that phase_assign tests per attractor (more: grid scan for all)
+static_assert(16 + (size_t)ASSIGN_STAGE * 25 + ((size_t)GRID_MAX * GRID_MAX + 16 * ASSIGN_STAGE) * 4 <= (size_t)SIM_USER_BYTES, "list length + staging of the new nodes + the map of the cells near one");
+// the largest x with sqrt(x) <= delta: the correctly rounded square root is monotone, so `sqrt(d2) <= delta` IS `d2 <= that x` for every d2
+OCTA_HD inline double sqrt_le_bound(double delta) {
+    double t = delta * delta;
+    while (sqrt(t) > delta) t = nextafter(t, 0.0);
+    while (sqrt(nextafter(t, INFINITY)) <= delta) t = nextafter(t, INFINITY);
+    return t;
+}
 OCTA_HD inline void phase_assign(const Blk &b, const SimArrays &A, int f, const double *att, int n_att, double delta) {
     SampleScalars *sc = A.sc;
     const int n_nodes = sc->n_nodes[f];
@@ -2347,15 +2379,141 @@ OCTA_HD inline void phase_assign(const Blk &b, const SimArrays &A, int f, const 
     // diagnostic build: the kd slots of the phase profile hold this phase's steps (both forests): active list, grid, queries, heads,
     // counts + starts, member scatter, member order
     long _at = (long)wall_clock64();
-#define ASP(slot) do { if (b.tid == 0) { long _t = (long)wall_clock64(); sc->kdprof[slot] += _t - _at; _at = _t; } } while (0)
+    // (-DOCTA_SIM_PROF_ASSIGN=2: slots 3..6 hold the steps in front of the grid instead -- set-up, staging of the new nodes, the
+    // attractors' pass, its closing barriers -- and the bookkeeping's steps are not timed)
+#define ASP_(slot) do { if (b.tid == 0) { long _t = (long)wall_clock64(); sc->kdprof[slot] += _t - _at; _at = _t; } } while (0)
+#define ASP(slot) do { if ((OCTA_SIM_PROF_ASSIGN + 0) != 2 || (slot) < 3) ASP_(slot); } while (0)
+#define ASP2(slot) do { if ((OCTA_SIM_PROF_ASSIGN + 0) == 2) ASP_(slot); } while (0)
 #else
 #define ASP(slot) do { } while (0)
+#define ASP2(slot) do { } while (0)
 #endif
-    // active node list (ascending id)
+    // What the previous assignment of this forest left (SimArrays::nn_prev / nn_d2). Node positions never change, a node's activity
+    // flag is only ever cleared, the attractor lists change by order-preserving compactions (which carry the entries along) and by
+    // appends, and delta only shrinks inside a mode. So for an attractor that was there last time and whose winner is still active the
+    // new winner is that node or one of the nodes created since -- a dozen per pass -- and the grid scan is needed only for the
+    // attractors appended since, those whose winner has grown a child, and every attractor after delta grew (a mode switch). The new
+    // nodes are staged in the table area and tested in exact double with the rule of the exact query below (smaller distance, then
+    // smaller id: an old winner keeps a tie) -- each by the attractors of the cells (of the grid's geometry) its delta-box touches: a
+    // chain of new nodes per cell in the table area. The attractors left over are collected in a list, so that whole waves run the
+    // grid scan. (Measured with EVERY new node tested by every attractor, or by every attractor of a cell near any new node: slower
+    // than the grid scan's ten single-precision visits -- assign_art 38.7 -> 57.9 / 52.5 ms per sample. New nodes grow where the
+    // attractors are, and a pass creates dozens of them.)
+    // -DOCTA_SIM_ASSIGN_NOCACHE: every attractor takes the grid scan, every time (the form until this memory existed; tests, A/B).
+    int n_q = n_att;               // grid queries of this call: all attractors, or the n_q listed in qlist
+    bool use_list = false;
+#ifdef OCTA_SIM_ASSIGN_NOCACHE
+    constexpr bool cached = false;
+    int *nn_prev = nullptr; double *nn_d2 = nullptr;
+    const int *qlist = nullptr;
+#else
+    int *nn_prev = A.nn_prev_of(f);
+    double *nn_d2 = A.nn_d2_of(f);
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool cached = true;
+#else
+    const bool cached = nn_prev != nullptr;      // (host harness without the two arrays)
+#endif
+    int *qlist = A.tmp_int;        // [OCAP] of the general scratch: free until the ordered pass
+    if (cached) {
+        const int n_c = OCTA_UNI(sc->n_cached[f] < n_att ? sc->n_cached[f] : n_att), n_old = OCTA_UNI(sc->n_nodes_cached[f]);
+        const int n_new = n_nodes - n_old;
+        if (OCTA_UNI((int)(n_c > 0 && delta <= sc->delta_cached[f] && n_new <= ASSIGN_STAGE))) {
+            int *qn = reinterpret_cast<int *>(b.user_of<2>());                                  // [1] length of qlist (+ padding)
+            double *sp = reinterpret_cast<double *>(b.user_of<2>() + 16);                        // [ASSIGN_STAGE][3] positions of the new nodes
+            unsigned char *sact = reinterpret_cast<unsigned char *>(sp + 3 * ASSIGN_STAGE);     // [ASSIGN_STAGE] their activity flags
+            int *head = reinterpret_cast<int *>(sact + ASSIGN_STAGE);                            // [nc * nc] per cell: chain of the active new nodes within (a little more than) delta of a point of the cell, in x and in y
+            int *link = head + GRID_MAX * GRID_MAX;                                              // [ASSIGN_STAGE][16] entry k * 16 + slot + 1 -> next entry of its cell's chain (0: end)
+            const double *npos = A.npos_of(f);
+            const unsigned char *nact = A.nact_of(f);
+            Grid Gn;                                                     // the cells of grid_build_once for this delta
+            {
+                const double cell = fmax(delta, 1.2 / GRID_MAX);
+                int nc = (int)ceil(1.2 / cell);
+                nc = nc < 1 ? 1 : (nc > GRID_MAX ? GRID_MAX : nc);
+                Gn.nx = Gn.ny = nc; Gn.x0 = Gn.y0 = -0.1; Gn.inv = 1.0 / cell; Gn.cell = cell;
+            }
+            const int nc = Gn.nx;
+            const double reach = delta * 1.000001;                       // (a superset costs a few exact tests; the exact tests decide)
+            const double d2_max = sqrt_le_bound(delta);
+            b.sync();                                                    // (the table area may still be read by the phase in front)
+            for (int c = b.tid; c < nc * nc; c += b.nth) head[c] = 0;
+            if (b.tid == 0) *qn = 0;
+            b.sync();
+            ASP2(3);
+            for (int k = b.tid; k < n_new; k += b.nth) {
+                const V3 q = ld3(npos + 3 * (size_t)(n_old + k));
+                const unsigned char act = nact[n_old + k];
+                st3(sp + 3 * k, q); sact[k] = act;
+                if (act) {
+                    const int cx0 = grid_cx(Gn, q.x - reach), cx1 = grid_cx(Gn, q.x + reach), cy0 = grid_cy(Gn, q.y - reach), cy1 = grid_cy(Gn, q.y + reach);
+                    // (2 x reach is a hair over two cells at most: the box touches at most 4 x 4 cells)
+                    for (int cy = cy0; cy <= cy1 && cy < cy0 + 4; cy++)
+                        for (int cx = cx0; cx <= cx1 && cx < cx0 + 4; cx++) {
+                            const int e = k * 16 + (cy - cy0) * 4 + (cx - cx0);
+                            link[e] = atomic_xchg_int(&head[cy * nc + cx], e + 1);
+                        }
+                }
+            }
+            b.sync();
+            ASP2(4);
+            // AB attractors per thread and round: their entries and positions are fetched together, then the activity flags of the AB winners
+            // (two round trips per round; one attractor at a time the pass was a chain of three dependent round trips per attractor, 41-49 ms per sample)
+            constexpr int AB = 8;
+            for (int a0 = b.tid; a0 < n_att; a0 += AB * b.nth) {
+                int j[AB];
+                V3 p[AB];
+                double bd[AB];
+                bool live[AB];
+#pragma unroll
+                for (int u = 0; u < AB; u++) {
+                    const int a = a0 + u * b.nth;
+                    const int ac = a < n_c ? a : 0;
+                    j[u] = a < n_c ? nn_prev[ac] : -2;               // -2: not in the memory
+                    bd[u] = nn_d2[ac];
+                    p[u] = ld3(att + 3 * (a < n_att ? a : 0));
+                }
+                OCTA_ISSUE_LOADS();
+                unsigned char jact[AB];
+#pragma unroll
+                for (int u = 0; u < AB; u++) jact[u] = nact[j[u] >= 0 ? j[u] : 0];
+                OCTA_ISSUE_LOADS();
+#pragma unroll
+                for (int u = 0; u < AB; u++) live[u] = j[u] == -1 || (j[u] >= 0 && jact[u] != 0);
+#pragma unroll
+                for (int u = 0; u < AB; u++) {
+                    const int a = a0 + u * b.nth;
+                    if (a >= n_att) continue;
+                    if (!live[u]) {                                      // appended since, or the winner has grown a child: the grid scan
+                        qlist[atomic_add_int(qn, 1)] = a;
+                        continue;
+                    }
+                    double d2b = j[u] >= 0 ? bd[u] : INFINITY;
+                    int best = j[u];
+                    for (int e = head[grid_cy(Gn, p[u].y) * nc + grid_cx(Gn, p[u].x)]; e; e = link[e - 1]) {      // (in any order: distance, then id)
+                        const int k = (e - 1) >> 4;
+                        const double d2 = sqdist(ld3(sp + 3 * k), p[u]);
+                        if (d2 < d2b || (d2 == d2b && n_old + k < best)) { d2b = d2; best = n_old + k; }
+                    }
+                    const int r = (best >= 0 && d2b <= d2_max) ? best : -1;      // sqrt(d2b) <= delta
+                    A.nn[a] = r;
+                    if (r != j[u]) nn_prev[a] = r;                   // (a winner beyond this delta stays beyond every later one until delta grows)
+                    if (r >= 0 && r != j[u]) nn_d2[a] = d2b;
+                }
+            }
+            ASP2(5);
+            b.sync();
+            n_q = OCTA_UNI(*qn);                                         // (the list's order varies from run to run; every query writes its own attractor's slots only)
+            b.sync();
+            use_list = true;
+            ASP2(6);
+        }
+    }
+#endif
+    ASP(0);
     // the grid over the ACTIVE nodes is built straight from the activity flags (no list of the active nodes: the node positions are
     // streamed once per pass, coalesced, instead of gathered through the list)
-    ASP(0);
-    {
+    if (n_q > 0) {
         Grid G = grid_build(b, A, A.npos_of(f), nullptr, n_nodes, delta, 1, true, A.nact_of(f));
         ASP(1);
         // (Round 4 measured a pruned nearest-neighbour search on a grid of four cells per radius -- rows outwards from the query's own, a
@@ -2367,7 +2525,8 @@ OCTA_HD inline void phase_assign(const Blk &b, const SimArrays &A, int f, const 
         // winner's distance lies in the band around delta (then its exact coordinates decide). Otherwise -- a near tie, including the
         // exact ties the index breaks -- the query is repeated on the exact coordinates (the nodes' own array, by item id).
         const float big = 3.0e38f;
-        for (int a = b.tid; a < n_att; a += b.nth) {
+        for (int q = b.tid; q < n_q; q += b.nth) {
+            const int a = use_list ? qlist[q] : q;
             const V3 p = ld3(att + 3 * a);
             const float pxf = (float)p.x, pyf = (float)p.y, pzf = (float)p.z;
             float m1 = big, m2 = big;
@@ -2395,6 +2554,10 @@ OCTA_HD inline void phase_assign(const Blk &b, const SimArrays &A, int f, const 
                 }
             }
             A.nn[a] = r;
+            if (cached) {                                                // what the next assignment starts from: the winner and its exact squared distance
+                nn_prev[a] = r;
+                if (r >= 0) nn_d2[a] = sqdist(ld3(G.src + 3 * r), p);
+            }
         }
         b.sync();
         ASP(2);
@@ -2517,10 +2680,16 @@ OCTA_HD inline void phase_assign(const Blk &b, const SimArrays &A, int f, const 
 #endif
     if (fits) book(fa + n_nodes, fa + n_nodes + n_groups, reinterpret_cast<unsigned *>(fa + n_nodes + 2 * n_groups), true);
     else book(A.gcount, A.tmp_int, A.sorted, false);
-    if (b.tid == 0) { sc->n_groups[f] = n_groups; sc->n_sorted[f] = n_sorted; }
+    if (b.tid == 0) {
+        sc->n_groups[f] = n_groups; sc->n_sorted[f] = n_sorted;
+        sc->assign_path[0] += n_att - n_q; sc->assign_path[1] += n_q;
+        if (cached) { sc->n_cached[f] = n_att; sc->n_nodes_cached[f] = n_nodes; sc->delta_cached[f] = delta; }
+    }
     b.sync();
     ASP(6);
 #undef ASP
+#undef ASP_
+#undef ASP2
 }
 
 // ------------------------------------------------------------------ per-node growth geometry
@@ -3211,24 +3380,37 @@ OCTA_HD inline void murray_flush_pending(const Blk &b, const SimArrays &A) {
 // the front, so the list is rewritten tile by tile -- a tile = the contiguous chunks of a group of threads; its kept points are
 // packed into LDS (each thread at its scanned offset), then copied to their final place with coalesced stores. One read of the
 // list, one write of the kept points that moved; no staging copy in HBM. `stage` is unused (kept for the callers' signature).
+// c_nn / c_d2 (optional): phase_assign's memory of the list's n points (SimArrays::nn_prev / nn_d2), moved the same way -- each tile a
+// second time through the LDS, behind its points.
 constexpr int COMPACT_TILE = 3072;     // points per LDS tile (72 KiB of the user area)
-OCTA_HD inline int compact_points(const Blk &b, double *pts, int n, const unsigned char *removed, double *stage) {
+constexpr int COMPACT_TILE_NN = 2048;  // ... when the list's assignment memory moves along: 48 KiB of points + 8 KiB of winners + 16 KiB of squared distances
+OCTA_HD inline int compact_points(const Blk &b, double *pts, int n, const unsigned char *removed, double *stage, int *c_nn = nullptr,
+                                  double *c_d2 = nullptr) {
     (void)stage;
     if (b.nth == 1) {                                                 // host build: one thread, a forward copy is in place already
         int w = 0;
         for (int i = 0; i < n; i++)
-            if (!removed[i]) { if (w != i) { pts[3 * w] = pts[3 * i]; pts[3 * w + 1] = pts[3 * i + 1]; pts[3 * w + 2] = pts[3 * i + 2]; } w++; }
+            if (!removed[i]) {
+                if (w != i) {
+                    pts[3 * w] = pts[3 * i]; pts[3 * w + 1] = pts[3 * i + 1]; pts[3 * w + 2] = pts[3 * i + 2];
+                    if (c_nn) { c_nn[w] = c_nn[i]; c_d2[w] = c_d2[i]; }
+                }
+                w++;
+            }
         return w;
     }
     double *tile = reinterpret_cast<double *>(b.user_of<16>());
-    static_assert((size_t)COMPACT_TILE * 24 <= (size_t)SIM_USER_BYTES, "compaction tile");
+    static_assert((size_t)COMPACT_TILE * 24 <= (size_t)SIM_USER_BYTES && (size_t)COMPACT_TILE_NN * 36 <= (size_t)SIM_USER_BYTES, "compaction tile");
 #if defined(__HIP_DEVICE_COMPILE__)
-    // a tile = COMPACT_TILE consecutive points; every wave takes a contiguous quarter of it, its lanes 64 consecutive points per step
+    // a tile = TILE consecutive points; every wave takes a contiguous quarter of it, its lanes 64 consecutive points per step
     // (coalesced flags and coordinates; round 4: a contiguous chunk per THREAD made every lane of a load touch its own cache line)
     const int lane = b.tid & 63, wv = b.tid >> 6, nw = (b.nth + 63) >> 6;
+    const int TILE = c_nn ? COMPACT_TILE_NN : COMPACT_TILE;
+    double *td = tile + 3 * COMPACT_TILE_NN;                          // [COMPACT_TILE_NN] squared distances, then as many winners
+    int *ti = reinterpret_cast<int *>(td + COMPACT_TILE_NN);
     int base = 0;                                                     // kept points in front of the tile = its first destination
-    for (int t0 = 0; t0 < n; t0 += COMPACT_TILE) {
-        const int tn = n - t0 < COMPACT_TILE ? n - t0 : COMPACT_TILE;
+    for (int t0 = 0; t0 < n; t0 += TILE) {
+        const int tn = n - t0 < TILE ? n - t0 : TILE;
         const int seg = ((tn + nw * 64 - 1) / (nw * 64)) * 64;
         const int s0 = t0 + (wv * seg < tn ? wv * seg : tn), s1 = s0 + seg < t0 + tn ? s0 + seg : t0 + tn;
         int c = 0;
@@ -3237,18 +3419,35 @@ OCTA_HD inline int compact_points(const Blk &b, double *pts, int n, const unsign
         const int kept = blk_scan(b, lane == 0 ? c : 0, &ex);
         if (base != t0 || kept != tn) {                               // (uniform) points in front of the first removal keep their place
             int at = __builtin_amdgcn_readfirstlane(ex);
-            for (int i0 = s0; i0 < s1; i0 += 64) {
-                const bool keep = i0 + lane < s1 && !removed[i0 + lane];
-                const unsigned long long m = __ballot(keep);
-                if (keep) {
-                    const int w = at + (int)__popcll(m & ((1ull << lane) - 1ull));
-                    const V3 v = ld3(pts + 3 * (size_t)(i0 + lane));
-                    tile[3 * w] = v.x; tile[3 * w + 1] = v.y; tile[3 * w + 2] = v.z;
+            constexpr int CB = 2;                                        // chunks of 64 points per round: their flags, coordinates and entries are fetched together
+            for (int i0 = s0; i0 < s1; i0 += CB * 64) {
+                bool keep[CB];
+                V3 v[CB];
+                int vn[CB] = {};
+                double vd[CB] = {};
+#pragma unroll
+                for (int u = 0; u < CB; u++) {
+                    const int i = i0 + u * 64 + lane, ic = i < s1 ? i : s1 - 1;      // (s1 > s0: s1 - 1 is a point of this segment)
+                    keep[u] = i < s1 && !removed[ic];
+                    v[u] = ld3(pts + 3 * (size_t)ic);
+                    if (c_nn) { vn[u] = c_nn[ic]; vd[u] = c_d2[ic]; }
                 }
-                at += (int)__popcll(m);
+                OCTA_ISSUE_LOADS();
+#pragma unroll
+                for (int u = 0; u < CB; u++) {
+                    const unsigned long long m = __ballot(keep[u]);
+                    if (keep[u]) {
+                        const int w = at + (int)__popcll(m & ((1ull << lane) - 1ull));
+                        tile[3 * w] = v[u].x; tile[3 * w + 1] = v[u].y; tile[3 * w + 2] = v[u].z;
+                        if (c_nn) { ti[w] = vn[u]; td[w] = vd[u]; }
+                    }
+                    at += (int)__popcll(m);
+                }
             }
             b.sync();
             for (int j = b.tid; j < kept * 3; j += b.nth) pts[(size_t)3 * base + j] = tile[j];
+            if (c_nn)
+                for (int j = b.tid; j < kept; j += b.nth) { c_nn[base + j] = ti[j]; c_d2[base + j] = td[j]; }
             b.sync();                                                 // the tile is reused; the next tile's sources lie behind this one's destinations
         }
         base += kept;
@@ -3257,6 +3456,16 @@ OCTA_HD inline int compact_points(const Blk &b, double *pts, int n, const unsign
 #else
     (void)tile;
     return n;    // (not reached: the host build has one thread)
+#endif
+}
+
+// does phase_assign's memory of forest f hold exactly the n attractors of its list (block-uniform)? Then a compaction carries it.
+OCTA_HD inline bool assign_memory_covers(const SimArrays &A, int f, int n) {
+#ifdef OCTA_SIM_ASSIGN_NOCACHE
+    (void)A; (void)f; (void)n;
+    return false;
+#else
+    return OCTA_UNI((int)(A.nn_prev_of(f) != nullptr && A.sc->n_cached[f] == n)) != 0;
 #endif
 }
 
@@ -3688,8 +3897,11 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
     }
 #endif
     // 6. delete the satisfied sinks (order-preserving)
-    int keep = compact_points(b, A.oxy, n_oxy, A.removed, A.tmp_dbl);
-    if (b.tid == 0) sc->n_oxy = keep;
+    // (phase_assign's memory of the sinks moves with them; it covers the whole list here -- sinks are appended only by phase_sample, in
+    // front of the assignment -- and is dropped if it ever does not)
+    const bool carry = assign_memory_covers(A, 0, n_oxy);
+    int keep = compact_points(b, A.oxy, n_oxy, A.removed, A.tmp_dbl, carry ? A.nn_prev[0] : nullptr, carry ? A.nn_d2[0] : nullptr);
+    if (b.tid == 0) { sc->n_oxy = keep; sc->n_cached[0] = carry ? keep : 0; }
     b.sync();
     OCTA_SUBPROF(sc, 15, t0);
 }
@@ -3717,8 +3929,10 @@ OCTA_HD inline void phase_satisfy_ven(const Blk &b, const SimArrays &A, const It
         }
         b.sync();
     }
-    int keep = compact_points(b, A.co2, n_co2, A.removed, A.tmp_dbl);
-    if (b.tid == 0) sc->n_co2 = keep;
+    // (phase_assign's memory of the sources moves with them: sources are appended only by phase_satisfy_art, behind this compaction)
+    const bool carry = assign_memory_covers(A, 1, n_co2);
+    int keep = compact_points(b, A.co2, n_co2, A.removed, A.tmp_dbl, carry ? A.nn_prev[1] : nullptr, carry ? A.nn_d2[1] : nullptr);
+    if (b.tid == 0) { sc->n_co2 = keep; sc->n_cached[1] = carry ? keep : 0; }
     b.sync();
 }
 

@@ -1,6 +1,6 @@
 """Per-phase device time of the simulator: one 128-sample full-length launch with the GPU to itself; 100 MHz timers of thread 0
 (octa_sim_stats slots 8..23 = prof[0..15], 24..31 = kdprof[0..7]), and how many O2 -> CO2 conversions built the kd order
-(octa_sim_kd_paths). usage: python tools/sim_phases.py [batch] [reps]"""
+(octa_sim_kd_paths) and how the assignments answered their attractors (octa_sim_assign_paths). usage: python tools/sim_phases.py [batch] [reps]"""
 import os
 import sys
 import time
@@ -37,6 +37,9 @@ def main():
         _native.check(sim._lib.octa_sim_kd_paths(sim._h, paths.ctypes.data), "octa_sim_kd_paths")
         cert, built = paths.mean(axis=0)
         print(f"  kd paths per sample: certified {cert:.1f}  built {built:.1f}  ({100 * cert / max(cert + built, 1e-9):.1f} % certified)")
+        _native.check(sim._lib.octa_sim_assign_paths(sim._h, paths.ctypes.data), "octa_sim_assign_paths")
+        inc, full = paths.mean(axis=0)       # attractors per sample answered from the forest's previous assignment / by the grid scan
+        print(f"  assign paths per sample: incremental {inc:.0f}  grid scan {full:.0f}  ({100 * inc / max(inc + full, 1e-9):.1f} % incremental)")
         if os.environ.get("OCTA_PHASES_RAW"):     # diagnostic builds keep counts in the kd slots: raw means, and the samples' scalar statistics
             print("  kd raw: " + "  ".join(f"{v:.0f}" for v in st[:, 24:32].mean(axis=0)))
             print("  stats[0:8] (err, py_pos, murray_steps, n_bif, respec, ...): " + "  ".join(f"{v:.0f}" for v in st[:, 0:8].mean(axis=0)))
