@@ -584,6 +584,33 @@ int octa_oof_2d(const float *d_in, double *d_out, int b, int h, int w, void *d_w
 /* The same without the final normalisation: d_out = R (the reference's OOF._compute_oof). */
 int octa_oof_2d_response(const float *d_in, double *d_out, int b, int h, int w, void *d_ws, void *stream);
 
+/* ---- Frangi vesselness baseline (configs/config_frangi.yml, reference models/frangi.py: skimage.filters.frangi) ----------
+ * Caller-owned device buffers and workspace, no context, as the OOF entry points. 1 <= h, w <= 4096, 1 <= b <= 65535, at most 8
+ * scales. A scale is given by scipy.ndimage's own 1-D weight tables at sigma / sqrt(2) (HOST memory, doubles): radius R and
+ * 2 (2 R + 1) values, the order-0 table then the order-1 table, offsets -R .. R (models/frangi.py gaussian_weights builds them).
+ * R <= 2^20, of which at most 96 taps per side may be non-zero (-2 otherwise). The input is d_in * in_scale in float32 (255 for
+ * the reference's convention, 1 for none), negated unless black_ridges. Hessian planes and eigenvalues are bit-identical to
+ * skimage's float32 ones on scipy.ndimage.gaussian_filter (mode 'reflect'); images are independent, results the same on every run. */
+
+/* Bytes of workspace the three calls below need for b images of h x w and n_scales scales (1 for the two single-scale calls);
+ * 0 for an invalid shape. */
+size_t octa_frangi_workspace_bytes(int b, int h, int w, int n_scales);
+
+/* Vesselness, float64 [b][h][w]: the maximum over the scales of exp(-rb^2 / (2 beta^2)) (1 - exp(-s^2 / (2 gamma^2))) (alpha plays
+ * no part in 2-D). radii: n_scales ints (host); weights: the scales' tables one after another (host). gamma = 0: per image
+ * max(s) / 2 of the FIRST scale (1 when that is 0), as skimage's gamma=None; gamma > 0: that value for every image. */
+int octa_frangi_2d(const float *d_in, double *d_out, int b, int h, int w, int n_scales, const int *radii, const double *weights, float in_scale,
+                   double beta, double gamma, int black_ridges, void *d_ws, void *stream);
+
+/* The Hessian of one scale, float32 [b][h][w] each: d_hrr, d_hrc, d_hcc (skimage hessian_matrix, use_gaussian_derivatives=True). */
+int octa_frangi_hessian(const float *d_in, float *d_hrr, float *d_hrc, float *d_hcc, int b, int h, int w, int radius, const double *weights,
+                        float in_scale, int black_ridges, void *d_ws, void *stream);
+
+/* The eigenvalues of that Hessian sorted by magnitude (d_l1 the smaller, the first of skimage's pair on a tie), float32 [b][h][w]
+ * each, and d_gamma float32 [b]: max(sqrt(l1^2 + l2^2)) / 2 per image, 1 when that is 0. */
+int octa_frangi_eigenvalues(const float *d_in, float *d_l1, float *d_l2, float *d_gamma, int b, int h, int w, int radius, const double *weights,
+                            float in_scale, int black_ridges, void *d_ws, void *stream);
+
 /* ---- N1-N4: space-colonisation vessel-graph simulator --------------------
  * Replaces, for B independent samples advanced in lock-step on the GPU:
  *   vessel_graph_generation/greenhouse.py:57-137 (Greenhouse.develop_forest) with

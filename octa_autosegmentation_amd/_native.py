@@ -142,6 +142,10 @@ SIGNATURES = {
     "octa_oof_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "octa_oof_2d": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "octa_oof_2d_response": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "octa_frangi_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "octa_frangi_2d": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_float, c_double, c_double, c_int, c_void_p, c_void_p]),
+    "octa_frangi_hessian": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]),
+    "octa_frangi_eigenvalues": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]),
     "octa_sim_kat_kd_order": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
 }
 
