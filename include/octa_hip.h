@@ -737,8 +737,9 @@ int octa_sim_trace(octa_sim *sim, int32_t *h_trace);
  * 4 O2->CO2, 6 assign-ven, 7 speculate-ven, 8 ordered-ven, 9 CO2 removal), then 8 timers of the kd-order build. */
 int octa_sim_stats(octa_sim *sim, int64_t *h_stats);
 
-/* How the O2 -> CO2 conversions of the last run ordered their CPython set, h_paths[B][2] int64: conversions whose table was certified
- * the same for every order of the cKDTree query results (no kd order built), conversions that built the kd order. */
+/* How the O2 -> CO2 conversions of the last run ordered their CPython set, h_paths[B][3] int64: conversions whose table was certified
+ * the same for every order of the cKDTree query results (no kd order built), conversions that ranked only the sinks of the groups the
+ * certificate flagged (partial kd order), conversions that built the kd order for every converted sink. */
 int octa_sim_kd_paths(octa_sim *sim, int64_t *h_paths);
 
 /* How the assignments of the last run found each attractor's nearest active node, h_paths[B][2] int64, summed over the iterations and
@@ -788,6 +789,10 @@ int octa_sim_fields(octa_sim *sim, int sample, double *h_oxy, int64_t cap_oxy, i
  * optional host flags need[n] (NULL = every rank is read) -> host tree.indices as int32[n]. With `need`
  * only the relative order of flagged points is defined. */
 int octa_sim_kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t *h_indices);
+
+/* The same build in the form the simulator's O2 -> CO2 conversion calls: the need flag rides in the sign of the single-precision x
+ * (every x must be >= 0), and only the bits `need_bits` (1..255) of a need byte count. */
+int octa_sim_kat_kd_order_signflag(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t need_bits, int32_t *h_indices);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,7 @@ using namespace OCTA_SIMK;
 #define octa_sim_spans OCTA_SIM_FN(spans)
 #define octa_sim_timing OCTA_SIM_FN(timing)
 #define octa_sim_kat_kd_order OCTA_SIM_FN(kat_kd_order)
+#define octa_sim_kat_kd_order_signflag OCTA_SIM_FN(kat_kd_order_signflag)
 struct OCTA_SIM_T;
 extern "C" void octa_sim_destroy(OCTA_SIM_T *S);
 extern "C" long long octa_sim_next_ticket(void);
@@ -1405,7 +1406,8 @@ extern "C" int octa_sim_stats(OCTA_SIM_T *S, int64_t *h_stats) {
 
 extern "C" int octa_sim_kd_paths(OCTA_SIM_T *S, int64_t *h_paths) {
     if (!S || !S->ran || !h_paths) { octa::set_error("octa_sim_kd_paths: run the simulation first"); return -2; }
-    for (int s = 0; s < S->B; s++) { h_paths[2 * s] = S->h_sc[s].kd_path[0]; h_paths[2 * s + 1] = S->h_sc[s].kd_path[1]; }
+    for (int s = 0; s < S->B; s++)
+        for (int k = 0; k < 3; k++) h_paths[3 * s + k] = S->h_sc[s].kd_path[k];
     return 0;
 }
 
@@ -1436,15 +1438,31 @@ extern "C" int octa_sim_fields(OCTA_SIM_T *S, int sample, double *h_oxy, int64_t
 #if !OCTA_SIM_LARGE
 namespace {
 __global__ void __launch_bounds__(SIM_THREADS)
-sim_kat_kd_kernel(const double *pts, int n, const unsigned char *need, idx_t *out_idx, idx_t *out_rank, float *xy, double zlo, double zhi) {
+sim_kat_kd_kernel(const double *pts, int n, const unsigned char *need, idx_t *out_idx, idx_t *out_rank, float *xy, double zlo, double zhi,
+                  int flag_in_sign, int need_bits) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     Blk b = {(int)threadIdx.x, (int)blockDim.x, smem};
-    kd_build(b, pts, n, out_idx, out_rank, xy, zlo, zhi, nullptr, need);
+    kd_build(b, pts, n, out_idx, out_rank, xy, zlo, zhi, nullptr, need, flag_in_sign != 0, (unsigned char)need_bits);
 }
+
+int kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t *h_indices, int flag_in_sign, int need_bits);
 }  // namespace
 
 extern "C" int octa_sim_kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t *h_indices) {
     if (!ctx || !h_pts || !h_indices || n < 0 || n > OCAP) { octa::set_error("octa_sim_kat_kd_order: bad arguments"); return -2; }
+    return kat_kd_order(ctx, h_pts, n, h_need, h_indices, 0, 0xff);
+}
+
+// the form phase_satisfy_art calls: the need flag rides in the sign of x (every x >= 0), need_bits selects the bits of a need byte that count
+extern "C" int octa_sim_kat_kd_order_signflag(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t need_bits, int32_t *h_indices) {
+    if (!ctx || !h_pts || !h_need || !h_indices || n < 0 || n > OCAP || need_bits <= 0 || need_bits > 0xff) { octa::set_error("octa_sim_kat_kd_order_signflag: bad arguments"); return -2; }
+    for (int64_t i = 0; i < n; i++)
+        if (!(h_pts[3 * i] >= 0.0)) { octa::set_error("octa_sim_kat_kd_order_signflag: x must be >= 0"); return -2; }
+    return kat_kd_order(ctx, h_pts, n, h_need, h_indices, 1, need_bits);
+}
+
+namespace {
+int kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t *h_indices, int flag_in_sign, int need_bits) {
     if (n == 0) return 0;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     double *d_pts = nullptr;
@@ -1462,7 +1480,7 @@ extern "C" int octa_sim_kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t
         OCTA_HIP_CHECK(hipMemcpy(d_need, h_need, n, hipMemcpyHostToDevice));
     }
     OCTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(sim_kat_kd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS));
-    hipLaunchKernelGGL(sim_kat_kd_kernel, dim3(1), dim3(SIM_THREADS), SIM_LDS, 0, d_pts, (int)n, d_need, d_idx, d_idx + n, d_xy, zlo, zhi);
+    hipLaunchKernelGGL(sim_kat_kd_kernel, dim3(1), dim3(SIM_THREADS), SIM_LDS, 0, d_pts, (int)n, d_need, d_idx, d_idx + n, d_xy, zlo, zhi, flag_in_sign, need_bits);
     OCTA_HIP_CHECK(hipGetLastError());
     std::vector<idx_t> h(n);
     OCTA_HIP_CHECK(hipMemcpy(h.data(), d_idx, sizeof(idx_t) * n, hipMemcpyDeviceToHost));
@@ -1470,6 +1488,7 @@ extern "C" int octa_sim_kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t
     (void)hipFree(d_pts); (void)hipFree(d_idx); (void)hipFree(d_xy); if (d_need) (void)hipFree(d_need);
     return 0;
 }
+}  // namespace
 
 #endif
 

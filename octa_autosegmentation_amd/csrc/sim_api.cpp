@@ -37,6 +37,7 @@ OCTA_DECL(S, octa_simS_impl)
 OCTA_DECL(L, octa_simL_impl)
 #undef OCTA_DECL
 int octa_simS_kat_kd_order(octa_ctx *, const double *, int64_t, const uint8_t *, int32_t *);
+int octa_simS_kat_kd_order_signflag(octa_ctx *, const double *, int64_t, const uint8_t *, int32_t, int32_t *);
 }
 
 // Persistent-kernel launches of this process so far, both builds (round 5). A generator that has just finished its own launch waits for the
@@ -136,4 +137,5 @@ extern "C" int octa_sim_fields(octa_sim *sim, int k, double *o, int64_t co, int6
 /* h_out4 as documented; a fifth query -- which build a configuration gets -- is octa_sim_is_large below. */
 extern "C" int octa_sim_geometry(int num_cus, int *h_out4) { return octa_simS_geometry(num_cus, h_out4); }
 extern "C" int octa_sim_kat_kd_order(octa_ctx *ctx, const double *p, int64_t n, const uint8_t *need, int32_t *o) { return octa_simS_kat_kd_order(ctx, p, n, need, o); }
+extern "C" int octa_sim_kat_kd_order_signflag(octa_ctx *ctx, const double *p, int64_t n, const uint8_t *need, int32_t bits, int32_t *o) { return octa_simS_kat_kd_order_signflag(ctx, p, n, need, bits, o); }
 extern "C" int octa_sim_is_large(const octa_sim *sim) { return sim && sim->large ? 1 : 0; }

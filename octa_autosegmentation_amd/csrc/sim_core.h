@@ -93,6 +93,22 @@ constexpr int KD_RANGES = OCAP / 17 + 1;  // ranges per kd level (a range that i
 constexpr int KD_TAB_BYTES_PER_RANGE = 4 * (int)sizeof(idx_t) + 1;   // range start / end of two levels + split dimension
 constexpr int KD_MAILBOX_OFF = OCAP * (int)sizeof(kdw_t) + ((KD_RANGES * KD_TAB_BYTES_PER_RANGE + 15) / 16) * 16;   // offset (after user()) of the swap mailbox / box table
 constexpr int KD_TEAM_MIN = 192;   // ranges at least this long get a whole wave, shorter ones 16 lanes
+// kd_build's box and key passes walk the concatenation of a level's listed ranges instead of [0, n) when those hold at most this many
+// elements (and at most half of n, in at most KD_SPARSE_RANGES ranges): with a sparse `need` the deep levels list one or two short
+// ranges, which the chunking of [0, n) hands to a few threads, one dependent fetch after the other. 0: always walk [0, n).
+// Measured at 512 / 2048 / 8192 (profiles/kd_partial_sparse_threshold.log): box + key passes 16.4 / 13.8 / 12.5 ms per sample.
+#ifndef OCTA_SIM_KD_SPARSE
+#define OCTA_SIM_KD_SPARSE 8192
+#endif
+constexpr int KD_SPARSE_MAX = OCTA_SIM_KD_SPARSE, KD_SPARSE_RANGES = 32;
+// kd_build's words in the collectives area (ints from Blk::coll()): behind blk_scan's two slots [0, 32) and the control words of the
+// phases that call it (phase_satisfy_art: 100..102; the others stay below 384), inside the area's 2 KiB
+constexpr int KD_COLL_PEND_N = 396;      // ranges whose exact extrema the whole workgroup measures
+constexpr int KD_COLL_LIVE_N = 397;      // elements in the listed ranges of the level being built
+constexpr int KD_COLL_EXTREMA = 400;     // [12]: max xyz, min xyz as six sortable 64-bit words
+constexpr int KD_COLL_PEND = 420;        // [64]: those ranges
+static_assert(KD_COLL_PEND_N >= 384 && KD_COLL_LIVE_N == KD_COLL_PEND_N + 1 && KD_COLL_EXTREMA % 2 == 0 && KD_COLL_EXTREMA > KD_COLL_LIVE_N &&
+              KD_COLL_PEND >= KD_COLL_EXTREMA + 12 && (KD_COLL_PEND + 64) * 4 <= 2048, "kd_build's collective words");
 #ifndef OCTA_SIM_THREADS
 #define OCTA_SIM_THREADS 256
 #endif
@@ -161,7 +177,8 @@ struct SampleScalars {
     long respec;
     long prof[16];  // accumulated 100 MHz ticks per phase (thread 0), see sim.hip
     long kdprof[8]; // kd_build breakdown: bbox, dim, gather, nth(wave), nth(thread), next-level, finalize
-    int kd_path[2]; // O2 -> CO2 conversions whose set order was certified without the kd order / that built it (phase_satisfy_art)
+    int kd_path[3]; // O2 -> CO2 conversions whose set order was certified without the kd order / with the kd ranks of the flagged groups only /
+                    // with the full kd order (phase_satisfy_art)
     // persistent form (sim.hip): a workgroup whose host answer does not arrive in time PARKS -- it records where to resume and
     // leaves the kernel; the host serves it at the kernel boundary and launches again
     int resume_it, resume_stage;   // stage 0: top of iteration resume_it; 1: behind its arterial mailbox
@@ -661,10 +678,16 @@ OCTA_HD inline void pyset_add(PySetView &s, int key, unsigned long long hash) {
 //   - no straddled resize: the key whose insertion resizes the table is the last of its group.
 // Then, group by group, each key lands on the first slot of its sequence that earlier groups do not hold, whatever the order inside its
 // group, and a resize re-inserts a table that is fixed already. Sequential form (one thread); the parallel replay of phase_satisfy_art
-// makes the same checks on its priority tables. own: [s_max] ints, ord0 / ord1: [D] ints. false also when a table would exceed s_max.
-OCTA_HD inline bool pyset_order_free(const int *dk, const int *dg, const unsigned long long *hashes, int D, int *own, int *ord0, int *ord1,
-                                     int s_max) {
-    int S = 8, n_prev = 0;
+// makes the same checks on its priority tables. own: [s_max] ints, ord0 / ord1: [D] ints.
+// xf (optional): one flag per group, the set X of phase_satisfy_art's ladder.
+//   xf == nullptr:   returns 1 at the first violation.
+//   !second (rung 0): every violation flags its key's group in xf and the walk carries on through all generations; returns their number.
+//   second (rung 1):  the groups flagged in xf arrive in their TRUE order and are exempt from both conditions; returns 1 at the first violation
+//                     of another group.
+// 0: certified. Also 1 when a table would exceed s_max.
+OCTA_HD inline int pyset_order_check(const int *dk, const int *dg, const unsigned long long *hashes, int D, int *own, int *ord0, int *ord1,
+                                     int s_max, unsigned char *xf, bool second) {
+    int S = 8, n_prev = 0, viol = 0;
     int *ord = ord0, *ord_next = ord1;
     while (true) {
         const int thr = (3 * (S - 1) + 4) / 5;            // the insertion that makes fill * 5 >= mask * 3 resizes the table
@@ -676,6 +699,7 @@ OCTA_HD inline bool pyset_order_free(const int *dk, const int *dg, const unsigne
             const int k = ord[p];
             const unsigned long long hsh = hashes[dk[k]];
             unsigned long long perturb = hsh, i = hsh & mask;
+            bool check = p >= n_prev && !(second && xf[dg[k]]);
             while (true) {
                 unsigned long long e = i;
                 int probes = (i + 9 <= mask) ? 9 : 0;
@@ -683,7 +707,10 @@ OCTA_HD inline bool pyset_order_free(const int *dk, const int *dg, const unsigne
                 do {
                     const int q = own[e];
                     if (q < 0) { own[e] = p; placed = true; break; }
-                    if (p >= n_prev && q >= n_prev && dg[q] == dg[k]) return false;    // (ord[q] = q behind the re-inserted entries)
+                    if (check && q >= n_prev && dg[q] == dg[k]) {                       // (ord[q] = q behind the re-inserted entries)
+                        if (!xf || second) return 1;
+                        xf[dg[k]] = 1; viol++; check = false;
+                    }
                     e++;
                 } while (probes--);
                 if (placed) break;
@@ -691,18 +718,26 @@ OCTA_HD inline bool pyset_order_free(const int *dk, const int *dg, const unsigne
                 i = (i * 5 + 1 + perturb) & mask;
             }
         }
-        if (D < thr) return true;
-        if (D > thr && dg[thr - 1] == dg[thr]) return false;
+        if (D < thr) return viol;
+        if (D > thr && dg[thr - 1] == dg[thr]) {
+            if (!xf) return 1;
+            if (!second) { xf[dg[thr]] = 1; viol++; }
+            else if (!xf[dg[thr]]) return 1;
+        }
         const int minused = upto > 50000 ? upto * 2 : upto * 4;
         int newS = 8;
         while (newS <= minused) newS <<= 1;
-        if (newS > s_max) return false;
+        if (newS > s_max) return 1;
         int c = 0;
         for (int e = 0; e < S; e++) if (own[e] >= 0) ord_next[c++] = ord[own[e]];   // re-insertion in the old table's slot order
         { int *t = ord; ord = ord_next; ord_next = t; }
         n_prev = upto;
         S = newS;
     }
+}
+OCTA_HD inline bool pyset_order_free(const int *dk, const int *dg, const unsigned long long *hashes, int D, int *own, int *ord0, int *ord1,
+                                     int s_max) {
+    return pyset_order_check(dk, dg, hashes, D, own, ord0, ord1, s_max, nullptr, false) == 0;
 }
 
 // ------------------------------------------------------------------ libstdc++ std::nth_element restated
@@ -1071,6 +1106,7 @@ OCTA_HD inline void atomic_min_u32(unsigned *p, unsigned v) {
 // Level-synchronous: range boundaries depend only on n; a range that became a leaf is marked done.
 // `need` (optional) flags the points whose rank will be read: a range without any such point is not
 // partitioned further (its internal order is never observed), which prunes most of the deep levels.
+// need_bits selects the bits of a `need` byte that count (phase_satisfy_art keeps two sets in one byte array).
 // LDS (78 KiB, kd_lds_layout below): packed elements u32[OCAP], per-level range tables, and the swap mailbox, whose area (plus the
 // tail) hosts the box table while no partition is running.
 constexpr int KD_TAB_OFF = OCAP * (int)sizeof(kdw_t);       // rs, re, rs2, re2 (idx_t each), rd (s8) per range
@@ -1084,7 +1120,7 @@ static_assert(KD_MAILBOX_OFF + (KD_BOX_BYTES > KD_MAILBOX_BYTES ? KD_BOX_BYTES :
 // whose x and y boxes are thinner than the slab, and those are measured exactly).
 OCTA_HD inline void kd_build(const Blk &b, const double *pts, int n, idx_t *out_idx, idx_t *out_rank,
                               float *xy, double zlo, double zhi, long *kdprof = nullptr, const unsigned char *need = nullptr,
-                              const bool flag_in_sign = false) {
+                              const bool flag_in_sign = false, const unsigned char need_bits = 0xff) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(OCTA_SIM_PROF_ASSIGN) && !defined(OCTA_SIM_PROF_SAMPLE) && !defined(OCTA_SIM_PROF_SET) && !defined(OCTA_SIM_PROF_MAIL) && !defined(OCTA_SIM_PROF_SEQ) && !defined(OCTA_SIM_PROF_SEQ2)
 #define KDP(slot) do { if (kdprof && b.tid == 0) { long _t = (long)wall_clock64(); kdprof[slot] += _t - _kt; _kt = _t; } } while (0)
     long _kt = (long)wall_clock64();
@@ -1109,9 +1145,12 @@ OCTA_HD inline void kd_build(const Blk &b, const double *pts, int n, idx_t *out_
         // round to nearest: x lies within one float spacing of it. flag_in_sign (the caller vouches for x >= 0: the sinks are valid
         // positions): the "rank is needed" flag rides in the sign of x -- one gather less per element and level of the box pass
         const float fx = (float)pts[3 * i];
-        xy[2 * i] = (flag_in_sign && need[i]) ? -fx : fx; xy[2 * i + 1] = (float)pts[3 * i + 1];
+        xy[2 * i] = (flag_in_sign && (need[i] & need_bits)) ? -fx : fx; xy[2 * i + 1] = (float)pts[3 * i + 1];
     }
-    if (b.tid == 0) { rs[0] = 0; re[0] = (idx_t)n; }
+    // elements in the listed ranges of the level being built. (Were a level ever to list more than KD_RANGES ranges, the count would include
+    // the dropped ones: harmless, the sparse walk skips positions behind the last range, and more than KD_SPARSE_RANGES ranges switch it off.)
+    int *live_n = b.coll() + KD_COLL_LIVE_N;
+    if (b.tid == 0) { rs[0] = 0; re[0] = (idx_t)n; *live_n = n; }
     const float z_up = f32_round_up(zhi), z_dn = f32_round_down(zlo);
     b.sync();
     int nr = (n > 16) ? 1 : 0;  // a range of <= leafsize points is a leaf: left in input order
@@ -1125,14 +1164,22 @@ OCTA_HD inline void kd_build(const Blk &b, const double *pts, int n, idx_t *out_
             rd[q] = 0;
         }
         b.sync();
+        // (uniform) a sparse level: the passes walk positions [0, live) of the ranges laid end to end; vs / ve: those of the range at hand
+        const int live = OCTA_UNI(*live_n);
+        const bool sparse = live <= KD_SPARSE_MAX && 2 * live <= n && nr <= KD_SPARSE_RANGES;
+        const int span = sparse ? live : n;
         {
-            const int chunk = ((n + b.nth - 1) / b.nth) | 1;      // odd: the lanes' element words lie in distinct LDS banks
-            const int i0 = b.tid * chunk, i1 = (i0 + chunk < n) ? i0 + chunk : n;
-            int q = 0;
-            if (i0 < i1) {  // last range starting at or before i0
+            const int chunk = ((span + b.nth - 1) / b.nth) | 1;      // odd: the lanes' element words lie in distinct LDS banks
+            const int i0 = b.tid * chunk, i1 = (i0 + chunk < span) ? i0 + chunk : span;
+            int q = 0, vs = 0, ve = 0;
+            if (i0 < i1 && !sparse) {  // last range starting at or before i0
                 int lo_ = 0, hi_ = nr - 1;
                 while (lo_ < hi_) { int mid = (lo_ + hi_ + 1) >> 1; if (rs[mid] <= i0) lo_ = mid; else hi_ = mid - 1; }
                 q = lo_;
+            }
+            if (i0 < i1 && sparse) {   // the range that holds position i0
+                ve = (int)re[0] - (int)rs[0];
+                while (i0 >= ve && q + 1 < nr) { q++; vs = ve; ve = vs + (int)re[q] - (int)rs[q]; }
             }
             bool have = false, hit = false;
             float mx[2] = {0, 0}, mn[2] = {0, 0};
@@ -1153,15 +1200,30 @@ OCTA_HD inline void kd_build(const Blk &b, const double *pts, int n, idx_t *out_
             for (int ib = i0; ib < i1; ib += KB) {
                 int eq[KB], eid[KB];
                 kdw_t ew[KB];
+                if (sparse) {
 #pragma unroll
-                for (int k = 0; k < KB; k++) ew[k] = kv[ib + k < i1 ? ib + k : i1 - 1];
+                    for (int k = 0; k < KB; k++) {
+                        const int i = ib + k;
+                        eq[k] = -1; eid[k] = 0;
+                        if (i < i1) {
+                            while (i >= ve && qw + 1 < nr) { qw++; cs = rs[qw]; ce = re[qw]; vs = ve; ve = vs + ce - cs; }
+                            const int at = cs + (i - vs);
+                            if (at < ce) { eq[k] = qw; eid[k] = at; }
+                        }
+                    }
 #pragma unroll
-                for (int k = 0; k < KB; k++) {
-                    const int i = ib + k;
-                    eq[k] = -1; eid[k] = 0;
-                    if (i < i1) {
-                        while (i >= ns) { qw++; cs = ns; ce = re[qw]; ns = qw + 1 < nr ? (int)rs[qw + 1] : 0x7fffffff; }
-                        if (i >= cs && i < ce) { eq[k] = qw; eid[k] = (int)(ew[k] & KD_IDX_MASK); }
+                    for (int k = 0; k < KB; k++) eid[k] = (int)(kv[eid[k]] & KD_IDX_MASK);      // (slot 0's word for the dead entries: any point will do)
+                } else {
+#pragma unroll
+                    for (int k = 0; k < KB; k++) ew[k] = kv[ib + k < i1 ? ib + k : i1 - 1];
+#pragma unroll
+                    for (int k = 0; k < KB; k++) {
+                        const int i = ib + k;
+                        eq[k] = -1; eid[k] = 0;
+                        if (i < i1) {
+                            while (i >= ns) { qw++; cs = ns; ce = re[qw]; ns = qw + 1 < nr ? (int)rs[qw + 1] : 0x7fffffff; }
+                            if (i >= cs && i < ce) { eq[k] = qw; eid[k] = (int)(ew[k] & KD_IDX_MASK); }
+                        }
                     }
                 }
                 float ex[KB], ey[KB];
@@ -1170,7 +1232,7 @@ OCTA_HD inline void kd_build(const Blk &b, const double *pts, int n, idx_t *out_
                 for (int k = 0; k < KB; k++) {
                     const float sx = xy[2 * eid[k]];
                     ex[k] = flag_in_sign ? fabsf(sx) : sx; ey[k] = xy[2 * eid[k] + 1];
-                    nd[k] = flag_in_sign ? (unsigned char)(f32_bits(sx) >> 31) : (need ? need[eid[k]] : (unsigned char)1);
+                    nd[k] = flag_in_sign ? (unsigned char)(f32_bits(sx) >> 31) : (need ? (unsigned char)(need[eid[k]] & need_bits) : (unsigned char)1);
                 }
 #pragma unroll
                 for (int k = 0; k < KB; k++) {
@@ -1192,9 +1254,10 @@ OCTA_HD inline void kd_build(const Blk &b, const double *pts, int n, idx_t *out_
             if (have) flush(q);
             if (hit) rd[q] = 1;
         }
-        int *pend_n = b.coll() + 396, *pend = b.coll() + 420;        // ranges whose exact extrema the whole workgroup measures (below)
+        int *pend_n = b.coll() + KD_COLL_PEND_N, *pend = b.coll() + KD_COLL_PEND;        // ranges whose exact extrema the whole workgroup measures (below)
         if (b.tid == 0) *pend_n = 0;
         b.sync();
+        if (b.tid == 0) *live_n = 0;      // (every thread has read it; step 4 counts the next level's behind further barriers)
         KDP(0);
         // split dimension = the first one with the largest spread
         for (int q = b.tid; q < nr; q += b.nth) {
@@ -1236,7 +1299,7 @@ OCTA_HD inline void kd_build(const Blk &b, const double *pts, int n, idx_t *out_
         b.sync();
         {
             const int n_pend = OCTA_UNI(*pend_n) < 64 ? OCTA_UNI(*pend_n) : 64;
-            unsigned long long *ex = reinterpret_cast<unsigned long long *>(b.coll() + 400);      // max xyz, min xyz as sortable words
+            unsigned long long *ex = reinterpret_cast<unsigned long long *>(b.coll() + KD_COLL_EXTREMA);      // max xyz, min xyz as sortable words
             for (int t = 0; t < n_pend; t++) {
                 const int q = OCTA_UNI(pend[t]);
                 for (int k = b.tid; k < 6; k += b.nth) ex[k] = k < 3 ? 0ull : ~0ull;
@@ -1270,21 +1333,32 @@ OCTA_HD inline void kd_build(const Blk &b, const double *pts, int n, idx_t *out_
         KDP(1);
         // 2. quantised split-dimension keys, element-parallel with the same chunking
         {
-            const int chunk = ((n + b.nth - 1) / b.nth) | 1;      // odd: the lanes' element words lie in distinct LDS banks
-            const int i0 = b.tid * chunk, i1 = (i0 + chunk < n) ? i0 + chunk : n;
-            int q = 0;
-            if (i0 < i1) {
+            const int chunk = ((span + b.nth - 1) / b.nth) | 1;      // odd: the lanes' element words lie in distinct LDS banks
+            const int i0 = b.tid * chunk, i1 = (i0 + chunk < span) ? i0 + chunk : span;
+            int q = 0, vs = 0, ve = 0;
+            if (i0 < i1 && !sparse) {
                 int lo_ = 0, hi_ = nr - 1;
                 while (lo_ < hi_) { int mid = (lo_ + hi_ + 1) >> 1; if (rs[mid] <= i0) lo_ = mid; else hi_ = mid - 1; }
                 q = lo_;
+            }
+            if (i0 < i1 && sparse) {
+                ve = (int)re[0] - (int)rs[0];
+                while (i0 >= ve && q + 1 < nr) { q++; vs = ve; ve = vs + (int)re[q] - (int)rs[q]; }
             }
             int qc = -1, d = -1;
             double mnd = 0, scale = 0;
             int cs = 0, ce = 0, ns = 0x7fffffff;
             if (i0 < i1) { cs = rs[q]; ce = re[q]; ns = q + 1 < nr ? (int)rs[q + 1] : 0x7fffffff; }
-            for (int i = i0; i < i1; i++) {
-                while (i >= ns) { q++; cs = ns; ce = re[q]; ns = q + 1 < nr ? (int)rs[q + 1] : 0x7fffffff; }
-                if (i < cs || i >= ce) continue;
+            for (int v = i0; v < i1; v++) {
+                int i = v;
+                if (sparse) {
+                    while (v >= ve && q + 1 < nr) { q++; cs = rs[q]; ce = re[q]; vs = ve; ve = vs + ce - cs; }
+                    i = cs + (v - vs);
+                    if (i >= ce) continue;
+                } else {
+                    while (i >= ns) { q++; cs = ns; ce = re[q]; ns = q + 1 < nr ? (int)rs[q + 1] : 0x7fffffff; }
+                    if (i < cs || i >= ce) continue;
+                }
                 if (q != qc) {
                     qc = q; d = rd[q];
                     if (d >= 0) {
@@ -1357,6 +1431,7 @@ OCTA_HD inline void kd_build(const Blk &b, const double *pts, int n, idx_t *out_
                 if (q < nr && rd[q] >= 0) {
                     s = rs[q]; e = re[q]; m = s + (e - s) / 2;
                     c = (m - s > 16 ? 1 : 0) + (e - m > 16 ? 1 : 0);
+                    if (c) atomic_add_int(live_n, (m - s > 16 ? m - s : 0) + (e - m > 16 ? e - m : 0));
                 }
                 int ex;
                 const int tot = blk_scan(b, c, &ex);
@@ -3487,8 +3562,12 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
     const double ek = P.eps_k, ek2 = ek * ek;
     long t0 = OCTA_SUBPROF_T0();
     for (int i = b.tid; i < n_oxy; i += b.nth) A.removed[i] = 0;
-    int *ctl = b.coll() + 100;         // [0] hit pairs, [1] set when the certificate of the provisional order fails (step 5)
-    if (b.tid == 0) { ctl[0] = 0; ctl[1] = 0; }
+    int *ctl = b.coll() + 100;         // [0] hit pairs, [1] / [2] set when the certificate of rung 0 / rung 1 fails (step 5)
+    if (b.tid == 0) { ctl[0] = 0; ctl[1] = 0; ctl[2] = 0; }
+    // X of the ladder below: one flag per new node (group). The nearest-node list is dead between the arterial growth and the venous assignment.
+    unsigned char *xf = reinterpret_cast<unsigned char *>(A.nn);
+    static_assert((size_t)NCAP <= (size_t)OCAP * sizeof(int), "group flags fit the nearest-node list");
+    for (int j = b.tid; j < n_new && j < NCAP; j += b.nth) xf[j] = 0;
     b.sync();
     // 1. (new node, sink) hits from a grid over the new nodes: raw pairs node_local << 14 | sink
     {
@@ -3558,29 +3637,69 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
     // The cKDTree order of a node's hits is observed only through the order in which they enter the CPython set `to_add`, and a
     // set's table depends on its insertion order only where keys contend for slots. A sink enters with the first new node that hits
     // it (its group): the order across groups is the node order, known without a tree. Pass 0 inserts each group's sinks in index
-    // order and certifies that no order inside a group could change the table (pyset_order_free); only where that fails does pass 1
-    // build the kd order and replay the exact insertion order (45 % of the builds certify).
-    bool set_in_lds = false, ranked = false;
+    // order and certifies that no order inside a group could change the table (pyset_order_check); 45 % of the conversions certify.
+    //
+    // The ladder. Rung 0 does not stop at the first violation of its certificate: it flags the GROUP of every violation -- a same-group
+    // blocker on a key's way to its slot, or a resizing key that is not the last of its group -- through all table generations. Call the
+    // flagged groups X (a refusal names one group in two cases of three, two keys in the median). Rung 1 builds the kd order only as deep
+    // as the sinks hit by X's nodes need it, gives X's pairs their kd rank (the others keep the sink index), replays the set in that
+    // mixed order and runs the certificate again with X's groups exempt from both conditions. Only if that refuses too (about one
+    // refusal in 400) does rung 2 rank every removed sink and replay the exact order.
+    //
+    // Why rung 1 is exact, by induction over the groups in arrival order. Assume the table in front of group g equals the reference's.
+    //   g in X: its keys arrive in the reference's order (the sinks of ALL of g's pairs are ranked, so the first arrivals among them
+    //     stand in cKDTree order; duplicates of earlier groups' keys never touch the table), so the table stays equal.
+    //   g not in X: the second certificate says that every slot a key of g passes before its own is held by an earlier group or by a
+    //     re-inserted entry. Each key therefore lands on the first slot of its sequence that earlier groups do not hold, whatever the
+    //     order inside g -- the argument of the one-rung certificate.
+    //   A resize happens at a fixed count of distinct keys. It is harmless if the resizing key is the last of its group, or if its
+    //     group is in X (true order): the re-insertion then works on a table that is fixed already.
+    // The choice of X needs no proof: ANY X is correct as long as the second certificate passes, so rung 0 may go on flagging on a table
+    // that was placed in provisional order.
+    // Every branch on the rung and on a certificate's outcome is block-uniform: the outcomes are read from ctl[] behind a barrier.
+    bool set_in_lds = false;
+    int rung = 0;                      // 0: provisional order; 1: kd ranks for X's groups; 2: kd ranks for every pair
+    bool from_partial = false;
+    // sink of a sorted / unsorted pair word on the current rung
+    auto sink_of = [&](unsigned pr) -> int {
+        const unsigned low = pr & IDX_MASK;
+        return (rung == 2 || (rung == 1 && xf[pr >> IDX_BITS])) ? (int)A.kd_idx[low] : (int)low;
+    };
 #ifdef OCTA_SIM_DEBUG_SAT
     int dbg_n_ins = -1, dbg_mask = -1, dbg_base = -1;
     const int dbg_n_co2_in = sc->n_co2;
 #endif
-    for (int pass = 0; pass < 2; pass++) {
-        ranked = pass > 0;
-        if (ranked) {
-            // 3. cKDTree order of the O2 list, only as deep as the hit sinks need it; pairs get kd ranks
-            kd_build(b, A.oxy, n_oxy, A.kd_idx, A.kd_rank, reinterpret_cast<float *>(A.tmp_dbl), 0.0, zext, sc->kdprof, A.removed, true);
+    while (true) {
+        const int vslot = rung == 1 ? 2 : 1;       // ctl slot of this rung's certificate
+        if (rung > 0) {
+            // 3. cKDTree order of the O2 list, only as deep as the sinks in `need` need it; pairs get kd ranks. Rung 1: need = the sinks hit by
+            //    X's nodes (bit 1 of their removal flag), ranks for X's pairs. Rung 2: need = every removed sink, ranks for every pair.
+            if (rung == 1) {
+                for (int i = b.tid; i < n_pairs; i += b.nth) {
+                    const unsigned pr = A.pairs[i];
+                    if (xf[pr >> IDX_BITS]) A.removed[pr & IDX_MASK] = 3;
+                }
+            } else if (OCTA_UNLIKELY(from_partial)) {
+                // X's pairs hold ranks of the pruned build: back to sink indices before the full build overwrites its kd_idx
+                for (int i = b.tid; i < n_pairs; i += b.nth) {
+                    const unsigned pr = A.pairs[i];
+                    if (xf[pr >> IDX_BITS]) A.pairs[i] = (pr & ~IDX_MASK) | (unsigned)A.kd_idx[pr & IDX_MASK];
+                }
+            }
+            b.sync();
+            const unsigned char need_bits = rung == 1 ? (unsigned char)2 : (unsigned char)0xff;
+            kd_build(b, A.oxy, n_oxy, A.kd_idx, A.kd_rank, reinterpret_cast<float *>(A.tmp_dbl), 0.0, zext, sc->kdprof, A.removed, true, need_bits);
 #if OCTA_SIM_DUP & 1
-            kd_build(b, A.oxy, n_oxy, A.kd_idx, A.kd_rank, reinterpret_cast<float *>(A.tmp_dbl), 0.0, zext, nullptr, A.removed, true);
+            kd_build(b, A.oxy, n_oxy, A.kd_idx, A.kd_rank, reinterpret_cast<float *>(A.tmp_dbl), 0.0, zext, nullptr, A.removed, true, need_bits);
 #endif
             for (int i = b.tid; i < n_pairs; i += b.nth) {
                 unsigned pr = A.pairs[i];
-                A.pairs[i] = (pr & ~IDX_MASK) | (unsigned)A.kd_rank[pr & IDX_MASK];
+                if (rung == 2 || xf[pr >> IDX_BITS]) A.pairs[i] = (pr & ~IDX_MASK) | (unsigned)A.kd_rank[pr & IDX_MASK];
             }
             b.sync();
             OCTA_SUBPROF(sc, 11, t0);
         }
-        // 4. sort the pairs: new nodes in order, hits in sink order (pass 0) or cKDTree order (pass 1)
+        // 4. sort the pairs: new nodes in order, hits in sink order (rung 0, and the groups outside X on rung 1) or cKDTree order
         unsigned *keys = reinterpret_cast<unsigned *>(b.user_of<32>());
         int n_pow2 = 1;
         while (n_pow2 < n_pairs) n_pow2 <<= 1;
@@ -3603,7 +3722,7 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
         //   fp[OCAP]: first arrival of a sink (duplicates of a key never touch the table), later own[slot] = priority of the slot's entry,
         //   at the end the slot's key (-1: empty) -- the table the read-out below walks;
         //   in_key / in_hash: arrivals; dk / dh: distinct keys in arrival order; ord0 / ord1: entry of a priority (this / next generation).
-        // in_key and dk hold node << IDX_BITS | sink: the node of a key's first arrival is its group, which the certificate of pass 0 compares.
+        // in_key and dk hold node << IDX_BITS | sink: the node of a key's first arrival is its group, which the certificates compare.
 #if defined(OCTA_SIM_PROF_SET)
         // diagnostic build: the kd slots of the phase profile hold the steps of the set replay: insert stream, distinct keys, generations,
         // key table, read-out
@@ -3623,7 +3742,7 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
                 int o = -1, take = 0;
                 unsigned long long hsh = 0;
                 if (i < n_pairs) {
-                    o = ranked ? (int)A.kd_idx[keys[i] & IDX_MASK] : (int)(keys[i] & IDX_MASK);   // the sorted pairs are still in the LDS
+                    o = sink_of(keys[i]);                          // the sorted pairs are still in the LDS
                     take = A.ven_near[o] ? 0 : 1;
                     hsh = A.hashes[o];                             // fetched beside the flag, not behind it
                 }
@@ -3684,28 +3803,41 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
                     }
                 }
                 b.sync();
-                if (!ranked) {
-                    // pass 0's certificate (pyset_order_free): every slot a new key passes before its own is held by a re-inserted entry or
-                    // by a key of an earlier group; the key that resizes the table is the last of its group. ord[p] = p behind n_prev.
+                if (rung < 2) {
+                    // the certificate (pyset_order_check): every slot a new key passes before its own is held by a re-inserted entry or by a
+                    // key of an earlier group; the key that resizes the table is the last of its group. ord[p] = p behind n_prev. Rung 0 flags
+                    // the group of every violation and carries on; rung 1 exempts the flagged groups and stops at a violation.
                     for (int p = n_prev + b.tid; p < upto; p += b.nth) {
                         const unsigned g = (unsigned)dk[p] >> IDX_BITS;
+                        if (rung == 1 && xf[g]) continue;
                         const unsigned long long hsh = dh[p];
                         unsigned long long i = hsh & mask, perturb = hsh;
                         int lin = 0, nlin = (i + 9 <= mask) ? 9 : 0;
                         while (true) {
                             const int q = own[(int)i + lin];
                             if (q == p) break;
-                            if (q == EMPTY) { atomic_or_int(&ctl[1], 1); break; }      // (not reached: the slots in front of a key's own are held)
-                            if (q >= n_prev && ((unsigned)dk[q] >> IDX_BITS) == g) { atomic_or_int(&ctl[1], 1); break; }
+                            // (q == EMPTY is not reached: the slots in front of a key's own are held)
+                            if (q == EMPTY || (q >= n_prev && ((unsigned)dk[q] >> IDX_BITS) == g)) {
+                                if (rung == 0) xf[g] = 1;
+                                atomic_or_int(&ctl[vslot], 1);
+                                break;
+                            }
                             if (lin < nlin) { lin++; continue; }
                             perturb >>= 5;
                             i = (i * 5 + 1 + perturb) & mask;
                             nlin = (i + 9 <= mask) ? 9 : 0; lin = 0;
                         }
                     }
-                    if (b.tid == 0 && D > thr && ((unsigned)dk[thr - 1] >> IDX_BITS) == ((unsigned)dk[thr] >> IDX_BITS)) atomic_or_int(&ctl[1], 1);
+                    if (b.tid == 0 && D > thr && ((unsigned)dk[thr - 1] >> IDX_BITS) == ((unsigned)dk[thr] >> IDX_BITS)) {
+                        const unsigned g = (unsigned)dk[thr] >> IDX_BITS;
+                        if (rung == 0) { xf[g] = 1; atomic_or_int(&ctl[vslot], 1); }
+                        else if (!xf[g]) atomic_or_int(&ctl[vslot], 1);
+                    }
+#ifdef OCTA_SIM_KD_PARTIAL_REFUSE
+                    if (b.tid == 0 && rung == 1) atomic_or_int(&ctl[vslot], 1);
+#endif
                     b.sync();
-                    if (ctl[1]) break;                            // (uniform) pass 1 replays the exact order
+                    if (rung == 1 && OCTA_UNLIKELY(ctl[vslot])) break;   // (uniform) rung 2 replays the exact order
                 }
                 if (D < thr) break;                               // no resize behind this generation: its table is the set
                 const int minused = upto > 50000 ? upto * 2 : upto * 4;
@@ -3774,7 +3906,7 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
             t_key = own;
             set_in_lds = true;
         }
-        if (set_in_lds && (ranked || !ctl[1])) {                        // (ctl[1] is read behind the replay's last barrier)
+        if (set_in_lds && (rung == 2 || !ctl[vslot])) {                 // (ctl[] is read behind the replay's last barrier)
             const int n_co2_0 = sc->n_co2;
             // read-out in slot order: a contiguous run of slots per thread, ONE block scan, then the converted sinks' coordinates fetched
             // eight at a time (one scan and one dependent fetch per 256 slots until round 4)
@@ -3817,20 +3949,23 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
             PySetView S;
             S.hash = A.set_hash; S.key = A.set_key; S.err = &sc->err; S.cap = SETCAP;
             pyset_init(S);
-            int *cw = reinterpret_cast<int *>(A.tmp_dbl);   // pass 0: distinct keys, their groups [OCAP] each; certificate tables [OCAP] x 2 + [2 OCAP]
+            int *cw = reinterpret_cast<int *>(A.tmp_dbl);   // rungs 0, 1: distinct keys, their groups [OCAP] each; certificate tables [OCAP] x 2 + [2 OCAP]
             static_assert((size_t)SETCAP / 2 <= (size_t)2 * OCAP, "certificate table");
             int D = 0;
             for (int i = 0; i < n_pairs; i++) {
                 const unsigned pr = A.pairs[i];
-                const int o = ranked ? (int)A.kd_idx[pr & IDX_MASK] : (int)(pr & IDX_MASK);
+                const int o = sink_of(pr);
                 if (!A.ven_near[o]) {
                     const int used = S.used;
                     pyset_add(S, o, A.hashes[o]);
-                    if (!ranked && S.used != used) { cw[D] = o; cw[OCAP + D] = (int)(pr >> IDX_BITS); D++; }
+                    if (rung < 2 && S.used != used) { cw[D] = o; cw[OCAP + D] = (int)(pr >> IDX_BITS); D++; }
                 }
             }
-            if (!ranked && !pyset_order_free(cw, cw + OCAP, A.hashes, D, cw + 4 * OCAP, cw + 2 * OCAP, cw + 3 * OCAP, SETCAP / 2)) ctl[1] = 1;
-            if (ranked || !ctl[1]) {
+            if (rung < 2 && pyset_order_check(cw, cw + OCAP, A.hashes, D, cw + 4 * OCAP, cw + 2 * OCAP, cw + 3 * OCAP, SETCAP / 2, xf, rung == 1)) ctl[vslot] = 1;
+#ifdef OCTA_SIM_KD_PARTIAL_REFUSE
+            if (rung == 1) ctl[vslot] = 1;
+#endif
+            if (rung == 2 || !ctl[vslot]) {
                 int n_co2 = sc->n_co2;
                 for (int e = 0; e <= S.mask; e++)
                     if (S.key[e] >= 0) {
@@ -3844,8 +3979,16 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
         }
         b.sync();
         OCTA_SUBPROF(sc, 14, t0);
-        if (!ranked && ctl[1]) continue;                              // (uniform: read behind the barrier above)
-        if (b.tid == 0) sc->kd_path[ranked ? 1 : 0]++;
+        if (rung < 2 && ctl[vslot]) {                                 // (uniform: read behind the barrier above)
+#ifdef OCTA_SIM_KD_NOPARTIAL
+            rung = 2;
+#else
+            from_partial = rung == 1;
+            rung++;
+#endif
+            continue;
+        }
+        if (b.tid == 0) sc->kd_path[rung]++;
         break;
     }
 #if defined(OCTA_SIM_DEBUG_SAT) && !defined(OCTA_SIM_ITER_PROF)
@@ -3860,7 +4003,7 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
         for (int o = b.tid; o < 2 * n_oxy; o += b.nth) mark[o] = 0;
         b.sync();
         for (int i = b.tid; i < n_pairs; i += b.nth) {
-            const int o = ranked ? (int)A.kd_idx[A.pairs[i] & IDX_MASK] : (int)(A.pairs[i] & IDX_MASK);
+            const int o = sink_of(A.pairs[i]);
             mark[o] = 1;
             if (!A.ven_near[o]) mark[n_oxy + o] = 1;
         }

@@ -33,10 +33,11 @@ def main():
         print(f"rep {rep}: wall {dt * 1e3:.0f} ms, kernel {res.timing['kernel_b_ms']:.0f} ms, per-sample phases sum {ph[:10].sum():.1f} ms")
         print("  " + "  ".join(f"{n} {v:.1f}" for n, v in zip(NAMES, ph)))
         print("  kd: " + "  ".join(f"{n} {v:.1f}" for n, v in zip(KD, kd)))
-        paths = np.zeros((B, 2), np.int64)       # O2 -> CO2 conversions per sample: set order certified without the kd order / kd order built
+        paths = np.zeros((B, 3), np.int64)       # O2 -> CO2 conversions per sample: set order certified without the kd order / partial / full kd order
         _native.check(sim._lib.octa_sim_kd_paths(sim._h, paths.ctypes.data), "octa_sim_kd_paths")
-        cert, built = paths.mean(axis=0)
-        print(f"  kd paths per sample: certified {cert:.1f}  built {built:.1f}  ({100 * cert / max(cert + built, 1e-9):.1f} % certified)")
+        cert, part, full = paths.mean(axis=0)
+        print(f"  kd paths per sample: certified {cert:.1f}  partial {part:.1f}  full {full:.1f}  ({100 * cert / max(cert + part + full, 1e-9):.1f} % certified)")
+        paths = np.zeros((B, 2), np.int64)
         _native.check(sim._lib.octa_sim_assign_paths(sim._h, paths.ctypes.data), "octa_sim_assign_paths")
         inc, full = paths.mean(axis=0)       # attractors per sample answered from the forest's previous assignment / by the grid scan
         print(f"  assign paths per sample: incremental {inc:.0f}  grid scan {full:.0f}  ({100 * inc / max(inc + full, 1e-9):.1f} % incremental)")
