@@ -370,6 +370,17 @@ int octa_head1_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, const 
 int octa_head1_nhwc_bwd(octa_ctx *ctx, const void *d_x, const void *d_dy, const float *d_w, int64_t npix, int C, void *d_dx,
                         float *d_dw, float *d_db, void *stream);
 
+/* 1x1 convolution head with 2 <= Cout <= 64 output channels and bias on the matrix cores (csrc/head.hip; UnetOutBlock with
+ * out_channels > 1, e.g. the 44 depth slices of the 3-D reconstruction set-up). d_x [N][hw][Cin] bf16 (NHWC), d_w [Cout][Cin] float32
+ * (rounded to bf16 in the kernel), d_bias float32[Cout] in device memory or NULL. The output side is CHANNEL-FIRST: d_y / d_dy
+ * [N][Cout][hw] bf16, y = bias + x w^T accumulated in float32 and rounded once. Backward: d_dx [N][hw][Cin] bf16, d_dw [Cout][Cin] and
+ * d_db [Cout] (NULL = not wanted) float32, overwritten; their per-workgroup partial sums (context scratch) are added in a fixed
+ * order, so two calls give identical bits. Cin in {32, 64}; anything else returns -2. hw may be odd. */
+int octa_headn_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_bias, int N, int64_t hw, int Cin, int Cout, void *d_y,
+                        void *stream);
+int octa_headn_nhwc_bwd(octa_ctx *ctx, const void *d_x, const void *d_dy, const float *d_w, int N, int64_t hw, int Cin, int Cout, void *d_dx,
+                        float *d_dw, float *d_db, void *stream);
+
 /* Every KxK convolution weight of a network into both layouts the MFMA kernels read, in ONE launch per optimiser step
  * (the master copies stay float32 torch parameters in the reference's state-dict layout, models/networks.py /
  * MONAI DynUNet: [Cout][Cin][K][K]). d_table: int64 [L][8] in device memory, one row per layer =

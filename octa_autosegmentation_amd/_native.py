@@ -136,6 +136,8 @@ SIGNATURES = {
     "octa_instnorm_lrelu_nhwc_fwd": (c_int, [c_void_p] * 7 + [c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "octa_instnorm_lrelu_head1_nhwc_fwd": (c_int, [c_void_p] * 9 + [c_int, c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_int, c_void_p]),
     "octa_head1_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p]),
+    "octa_headn_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "octa_headn_nhwc_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "octa_conv3x3_c1_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "octa_fft2_c2c_f64_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "octa_fft2_c2c_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -631,7 +631,9 @@ class ImageToImageTranslationd(MapTransform):
 
 class LoadImaged(MapTransform):
     """PNG -> float32 tensor on the GPU. MONAI's PILReader hands images over with the first two axes swapped (its
-    `reverse_indexing`: [W, H(, C)]); the configs undo that with Rotate90d(k=1) + Flipd(spatial_axis=0), so the swap is kept."""
+    `reverse_indexing`: [W, H(, C)]); the configs undo that with Rotate90d(k=1) + Flipd(spatial_axis=0), so the swap is kept.
+    `.nii` / `.nii.gz` (octa_autosegmentation_amd/nifti.py) and `.npy` volumes arrive in their stored axis order: only the PIL reader
+    swaps."""
 
     def __init__(self, keys, allow_missing_keys: bool = False, image_only: bool = True, **unused) -> None:
         super().__init__(keys, allow_missing_keys)
@@ -640,10 +642,17 @@ class LoadImaged(MapTransform):
         from PIL import Image
         data = dict(data)
         for key in self.present(data):
-            a = np.asarray(Image.open(data[key]))
-            if a.dtype == bool:
-                a = a.astype(np.uint8)
-            a = np.swapaxes(a, 0, 1)
+            path = str(data[key])
+            if path.endswith((".nii", ".nii.gz")):
+                from .. import nifti
+                a = nifti.read(path)[0]
+            elif path.endswith(".npy"):
+                a = np.load(path)
+            else:
+                a = np.asarray(Image.open(data[key]))
+                if a.dtype == bool:
+                    a = a.astype(np.uint8)
+                a = np.swapaxes(a, 0, 1)
             data[key] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(default_device())
         return data
 
@@ -843,6 +852,23 @@ class CastToTyped(MapTransform):
         return data
 
 
+class SelectSlice(MapTransform):
+    """`data[key][slices]` with one slice per `[start, end]` pair of slice_selection, applied from dim 0 (the 3-D reconstruction set-up
+    keeps depth slices 5 .. -4 of the channel-first label volume). None = identity (the reference raises AttributeError there)."""
+
+    def __init__(self, keys, allow_missing_keys: bool = False, slice_selection=None) -> None:
+        super().__init__(keys, allow_missing_keys)
+        self.slice_selection = tuple(slice(s, e) for s, e in slice_selection) if slice_selection else None
+
+    def __call__(self, data):
+        if self.slice_selection is None:
+            return data
+        data = dict(data)
+        for key in self.present(data):
+            data[key] = data[key][self.slice_selection]
+        return data
+
+
 # ---- post-processing (array transforms applied to one decollated sample, configs `post_processing`) ------------------
 
 class Activations:
@@ -893,11 +919,21 @@ class CastToType:
         return x.to(self.dtype)
 
 
+class AsChannelLast:
+    """[C, ...] -> [..., C] (MONAI's AsChannelLast): the depth slices of a 3-D prediction become the last axis of the volume."""
+
+    def __init__(self, channel_dim=0, **unused):
+        self.channel_dim = int(channel_dim)
+
+    def __call__(self, x):
+        return x.movedim(self.channel_dim, -1)
+
+
 TRANSFORMS = {c.__name__: c for c in (
     LoadGraphAndFilterByRandomRadiusd, ToGrayScaled, SpeckleBrightnesd, AddRandomBackgroundNoised, ImageToImageTranslationd,
     BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact, MentenAugmentationd, NoiseModeld, RandomDecreaseResolutiond,
     LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, Flipd, RandFlipd, Rotate90d, RandRotate90d, RandRotated, AsDiscreted,
-    CastToTyped, Activations, AsDiscrete, RemoveSmallObjects, Resize, CastToType)}
+    CastToTyped, SelectSlice, Activations, AsDiscrete, RemoveSmallObjects, Resize, CastToType, AsChannelLast)}
 
 
 def get_data_augmentations(aug_config, seed=None, dtype=torch.float32):

@@ -60,6 +60,12 @@ class DiceBCELoss:
         if (USE_FUSED_LOSS and self.sigmoid and y_pred.is_cuda and y_pred.dtype in (torch.float32, torch.bfloat16)
                 and y_pred.shape == y.shape and (y_pred.dim() < 2 or y_pred.shape[1] == 1)):
             return _FusedDiceBCE.apply(y_pred, y, self.dice.smooth_nr, self.dice.smooth_dr)   # one channel: per-sample sums
+        if (USE_FUSED_LOSS and self.sigmoid and y_pred.is_cuda and y_pred.dtype in (torch.float32, torch.bfloat16)
+                and y_pred.shape == y.shape and y_pred.dim() >= 3):
+            # several channels: Dice is a mean over (sample, channel), BCE a mean over all elements -> B * C rows of H * W on the
+            # contiguous channel-first logits (what the N-channel head writes)
+            rows = y_pred.shape[0] * y_pred.shape[1]
+            return _FusedDiceBCE.apply(y_pred.contiguous().view(rows, -1), y.contiguous().view(rows, -1), self.dice.smooth_nr, self.dice.smooth_dr)
         return (self.dice(y_pred, y) + self.bce(y_pred, y)) / 2
 
 

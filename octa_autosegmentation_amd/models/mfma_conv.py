@@ -918,12 +918,53 @@ def instance_norm_leaky_relu_head1_nhwc(x, gamma, beta, negative_slope, eps, hea
     return _InstNormLReLUHead1NHWC.apply(x, gamma, beta, negative_slope, eps, head_weight, head_bias, partials)
 
 
+class _HeadNNHWC(torch.autograd.Function):
+    """1x1 convolution to 2..64 channels with bias on the matrix cores (csrc/head.hip): NHWC in, CHANNEL-FIRST [N, Cout, H, W] out."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = x.contiguous()
+        n, h, w, c = x.shape
+        cout = weight.shape[0]
+        wv = weight.reshape(cout, c).float().contiguous()
+        bv = bias.float().contiguous() if bias is not None else None
+        y = torch.empty((n, cout, h, w), dtype=torch.bfloat16, device=x.device)
+        _native.launch("octa_headn_nhwc_fwd", x.device, x, wv, bv, n, h * w, c, cout, y)
+        ctx.save_for_backward(x, wv)
+        ctx.w_shape, ctx.w_dtype, ctx.has_bias = weight.shape, weight.dtype, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wv = ctx.saved_tensors
+        dy = _bf16c(dy)
+        n, h, w, c = x.shape
+        cout = wv.shape[0]
+        dx = torch.empty_like(x)
+        dw = torch.empty((cout, c), dtype=torch.float32, device=x.device)
+        db = torch.empty(cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+        _native.launch("octa_headn_nhwc_bwd", x.device, x, dy, wv, n, h * w, c, cout, dx, dw, db)
+        return dx, dw.view(ctx.w_shape).to(ctx.w_dtype), (db.to(ctx.w_dtype) if ctx.has_bias else None)
+
+
+def headn_ok(cin, weight):
+    """The matrix-core head applies (and conv1x1_bias_nhwc's result is channel-first). Inside networks.vendor_reference() the old GEMM is
+    wanted: the reference side of the head's parity test."""
+    from . import networks
+    return cin in (32, 64) and 2 <= weight.shape[0] <= 64 and weight.shape[1] == cin and networks._REFERENCE_DEPTH[0] == 0
+
+
 def conv1x1_bias_nhwc(x, weight, bias):
-    """1x1 convolution head: weight [Cout, Cin, 1, 1], bias [Cout] -> [N,H,W,Cout] bf16."""
+    """1x1 convolution head: weight [Cout, Cin, 1, 1], bias [Cout]. One output channel -> [N,H,W,1] bf16 (streaming kernels); 2..64
+    output channels from 32 or 64 -> CHANNEL-FIRST contiguous [N,Cout,H,W] bf16 (csrc/head.hip: what the loss and the post-processing
+    read); any other shape -> [N,H,W,Cout] bf16 through the vendor GEMM (an error under OCTA_STRICT=1)."""
     if weight.shape[0] == 1 and x.shape[-1] % 8 == 0 and x.shape[-1] <= 256 and 256 % (x.shape[-1] // 8) == 0:
         return _Head1NHWC.apply(x, weight, bias)
+    if x.dtype == torch.bfloat16 and headn_ok(x.shape[-1], weight):
+        return _HeadNNHWC.apply(x, weight, bias)
     from . import networks
-    networks._vendor_fallback("DynUNet output block (NHWC)", f"{x.shape[-1]} -> {weight.shape[0]} channels: GEMM through hipBLASLt (the streaming head covers one output channel)")
+    networks._vendor_fallback("DynUNet output block (NHWC)", f"{x.shape[-1]} -> {weight.shape[0]} channels: GEMM through hipBLASLt (the streaming head covers one output "
+                              "channel, the matrix-core head 2..64 channels from 32 or 64)")
     n, h, w, cin = x.shape
     y = torch.matmul(x.reshape(n * h * w, cin), weight.reshape(weight.shape[0], cin).t().to(torch.bfloat16))
     if bias is not None:

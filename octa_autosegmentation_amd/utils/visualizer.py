@@ -37,11 +37,13 @@ def _save_strip(path, images):
 
 
 def plot_single_image(save_dir: str, input: torch.Tensor, name: str = None):
-    """test.py's prediction file: `<save_dir>/<name without extension>.png` = uint8(input * 255) (visualizer.py:330-339)."""
+    """test.py's prediction file: `<save_dir>/<name without extension>.png` = uint8(input * 255) (visualizer.py:330-339); a squeezed
+    input with more than 2 dims (the 3-D reconstruction set-up) goes to `<name without extension>.nii.gz` as that uint8 volume."""
     from .. import _native
     a = np.ascontiguousarray((input.squeeze().detach().float().cpu().numpy() * 255).astype(np.uint8))
-    if a.ndim != 2:
-        raise NotImplementedError("3-D predictions (nifti) are outside the MI355X hot path")
+    if a.ndim > 2:
+        from .. import nifti
+        return nifti.write(os.path.join(save_dir, ".".join(name.split(".")[:-1]) + ".nii.gz"), a)
     path = os.path.join(save_dir, ".".join(name.split(".")[:-1]) + ".png")
     _native.call("octa_png_write_gray8", path.encode(), a.ctypes.data, a.shape[1], a.shape[0], -1)
     return path
@@ -51,6 +53,10 @@ def plot_sample(save_dir: str, input: torch.Tensor, pred: torch.Tensor, truth: t
                 **unused) -> str:
     suffix = "_" + suffix if suffix else ""
     imgs = [_to_u8(input), _to_u8(pred)] + ([_to_u8(truth)] if truth is not None else [])
+    if imgs[0].ndim == 3:
+        imgs[0] = imgs[0][0]
+    if imgs[1].ndim == 3:              # volumes [X, Y, Z] (3-D reconstruction): maximum projection along depth, as the reference plots them
+        imgs[1:] = [np.ascontiguousarray(a.max(axis=-1)) for a in imgs[1:]]
     return _save_strip(os.path.join(save_dir, f"sample{suffix}.png"), imgs)
 
 

@@ -1,7 +1,7 @@
 """Drop-in for the reference's visualize_vessel_graphs.py on MI355X: CSV graphs -> image / binarised label PNG /
-3-D volume with the reference's flags (`--source_dir --out_dir --resolution --save_2d/--no_save_2d --save_3d
---save_3d_as --mip_axis --binarize --num_samples --max_dropout_prob --ignore_z --threads`). Rendering runs in
-the HIP rasteriser / voxeliser; label PNGs are the bit-exact Floyd-Steinberg binarisation (mode "1")."""
+3-D volume (`.nii.gz` through octa_autosegmentation_amd/nifti.py, or `.npy`) with the reference's flags
+(`--source_dir --out_dir --resolution --save_2d/--no_save_2d --save_3d --save_3d_as --mip_axis --binarize --num_samples
+--max_dropout_prob --ignore_z --threads`). Rendering runs in the HIP rasteriser / voxeliser; label PNGs are the bit-exact Floyd-Steinberg binarisation (mode "1")."""
 import argparse
 import os
 import pickle
@@ -37,15 +37,13 @@ def main(argv=None):
     assert os.path.isdir(args.source_dir), f"The provided source directory {args.source_dir} does not exist."
     assert args.mip_axis in [0, 1, 2], "The axis must be '0' (x), '1' (y) or '2' (z)."
     assert args.save_3d or args.save_2d, "You must either activate saving the 2D image or the 3D volume."
-    if args.save_3d and args.save_3d_as == ".nii.gz":
-        raise NotImplementedError("nifti output needs nibabel, which is not part of the MI355X image; use --save_3d_as .npy")
     os.makedirs(args.out_dir, exist_ok=True)
     img_res = [int(r) for i, r in enumerate(resolution) if not (len(resolution) == 3 and i == args.mip_axis)]
 
     import csv
     import torch
     from concurrent.futures import ThreadPoolExecutor
-    from octa_autosegmentation_amd import graph_io
+    from octa_autosegmentation_amd import graph_io, nifti
     from octa_autosegmentation_amd.output_files import SampleFileWriter, default_threads
     from octa_autosegmentation_amd.vessel_graph_generation import tree2img
     files = sorted(glob(os.path.join(args.source_dir, "**", "*.csv"), recursive=True), key=_natural_key)[:args.num_samples]
@@ -82,9 +80,13 @@ def main(argv=None):
         if args.save_3d:
             vol, black_dict = tree2img.voxelize_forest(forest, [int(r) for r in resolution], max_dropout_prob=args.max_dropout_prob, ignore_z=args.ignore_z)
             out_name = name + ("_3d_label" if args.binarize else "_3d")
-            if args.binarize:
-                vol = vol >= 1
-            np.save(os.path.join(args.out_dir, out_name + ".npy"), vol.astype(np.bool_))
+            if args.save_3d_as == ".nii.gz":
+                # what the reference hands to Nifti1Image: the voxeliser's array in its own dtype, 0 / 1 in that dtype with --binarize
+                nifti.write(os.path.join(args.out_dir, out_name + ".nii.gz"), (vol >= 1).astype(vol.dtype) if args.binarize else vol)
+            else:
+                if args.binarize:
+                    vol = vol >= 1
+                np.save(os.path.join(args.out_dir, out_name + ".npy"), vol.astype(np.bool_))
             if args.max_dropout_prob > 0:
                 with open(os.path.join(args.out_dir, out_name + "_blackdict.pkl"), 'wb') as f:
                     pickle.dump(black_dict, f)
