@@ -544,7 +544,10 @@ int nhwc_group(int B, size_t bytes_per_image) {
 }
 
 int nhwc_check(const char *who, int B, int C, int64_t hw) {
-    if (B <= 0 || hw <= 0 || C <= 0 || C % 8 || C > NHWC_MAXC || NT % (C / 8) != 0 && C / 8 > NT) { octa::set_error("%s: C must be a multiple of 8, <= %d (got B=%d C=%d)", who, NHWC_MAXC, B, C); return -2; }
+    // every channel group needs a thread of the block (C / 8 <= NT). A group count that does not divide NT is supported: the
+    // NT % (C / 8) threads past the last whole pixel lane idle (C = 24, 40: tests/test_norm_gpu.py cases 3 and 4)
+    static_assert(NHWC_MAXC / 8 <= NT, "a block holds at least one pixel lane of every channel group");
+    if (B <= 0 || hw <= 0 || C <= 0 || C % 8 || C > NHWC_MAXC || C / 8 > NT) { octa::set_error("%s: C must be a multiple of 8, <= %d (got B=%d C=%d)", who, NHWC_MAXC, B, C); return -2; }
     if (B > 65535) { octa::set_error("%s: B > 65535", who); return -2; }
     return 0;
 }
