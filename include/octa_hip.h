@@ -805,6 +805,15 @@ int octa_sim_kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const u
  * (every x must be >= 0), and only the bits `need_bits` (1..255) of a need byte count. */
 int octa_sim_kat_kd_order_signflag(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t need_bits, int32_t *h_indices);
 
+/* Known-answer hook for the sampling of oxygen sinks (greenhouse.py:319-341) of the default simulator build: ONE call of the phase in one
+ * workgroup. Host candidates [n_cand][3] (n_cand <= 8192), arterial nodes [n_art][3] with radii [n_art], sinks h_oxy [n_oxy][3] with
+ * room for cap_oxy; eps_n / eps_k / eps_s as the iteration table holds them (already scaled); h_cst8 = param_scale, the space's size
+ * x / y / z, geometry_size, FAZ centre x / y, FAZ radius. On return h_oxy holds the list behind the call (the accepted candidates
+ * appended in order, at most cap_oxy entries copied) and *h_n_out its length. -3: the phase set an error bit (a capacity). */
+int octa_sim_kat_sample(octa_ctx *ctx, const double *h_cand, int64_t n_cand, const double *h_npos, const double *h_nrad, int64_t n_art,
+                        double *h_oxy, int64_t n_oxy, int64_t cap_oxy, double eps_n, double eps_k, double eps_s, const double *h_cst8,
+                        int64_t *h_n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,7 @@ using namespace OCTA_SIMK;
 #define octa_sim_timing OCTA_SIM_FN(timing)
 #define octa_sim_kat_kd_order OCTA_SIM_FN(kat_kd_order)
 #define octa_sim_kat_kd_order_signflag OCTA_SIM_FN(kat_kd_order_signflag)
+#define octa_sim_kat_sample OCTA_SIM_FN(kat_sample)
 struct OCTA_SIM_T;
 extern "C" void octa_sim_destroy(OCTA_SIM_T *S);
 extern "C" long long octa_sim_next_ticket(void);
@@ -1488,7 +1489,68 @@ int kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h
     (void)hipFree(d_pts); (void)hipFree(d_idx); (void)hipFree(d_xy); if (d_need) (void)hipFree(d_need);
     return 0;
 }
+
+// phase_sample alone, one workgroup, on uploaded inputs (tests): the sink list behind the call
+__global__ void __launch_bounds__(SIM_THREADS)
+sim_kat_sample_kernel(SimArrays A, SimConst C, IterParams P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    Blk b = {(int)threadIdx.x, (int)blockDim.x, smem};
+    phase_sample(b, A, C, P, 0);
+}
 }  // namespace
+
+extern "C" int octa_sim_kat_sample(octa_ctx *ctx, const double *h_cand, int64_t n_cand, const double *h_npos, const double *h_nrad, int64_t n_art,
+                                   double *h_oxy, int64_t n_oxy, int64_t cap_oxy, double eps_n, double eps_k, double eps_s, const double *h_cst8,
+                                   int64_t *h_n_out) {
+    if (!ctx || !h_cst8 || !h_n_out || n_cand < 0 || n_cand > NCANDCAP || n_art < 0 || n_art > NCAP || n_oxy < 0 || n_oxy > OCAP || cap_oxy < n_oxy ||
+        (n_cand && !h_cand) || (n_art && (!h_npos || !h_nrad)) || (cap_oxy && !h_oxy)) {
+        octa::set_error("octa_sim_kat_sample: bad arguments");
+        return -2;
+    }
+    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
+    SimConst C;
+    memset(&C, 0, sizeof(C));
+    C.ps = h_cst8[0]; C.sx = h_cst8[1]; C.sy = h_cst8[2]; C.sz = h_cst8[3]; C.gs = h_cst8[4]; C.fc0 = h_cst8[5]; C.fc1 = h_cst8[6];
+    SampleScalars sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.faz_radius = h_cst8[7]; sc.n_nodes[0] = (int)n_art; sc.n_oxy = (int)n_oxy;
+    IterParams P;
+    memset(&P, 0, sizeof(P));
+    P.N = (int)n_cand; P.eps_n = eps_n; P.eps_k = eps_k; P.eps_s = eps_s;
+    // one allocation: sinks, general double scratch, grid points, candidates, node positions, radii | int scratch | byte scratch | scalars
+    const size_t n_dbl = (size_t)OCAP * 3 * 2 + (size_t)GRID_N * 3 + (size_t)NCANDCAP * 3 + (size_t)NCAP * 4;
+    const size_t n_int = (size_t)OCAP + 2 * (size_t)NCANDCAP, n_byte = (size_t)(OCAP > NCANDCAP ? OCAP : NCANDCAP);
+    const size_t off_int = n_dbl * 8, off_byte = off_int + n_int * 4, off_sc = (off_byte + n_byte + 15) & ~(size_t)15;
+    unsigned char *d = nullptr;
+    OCTA_HIP_CHECK(hipMalloc(&d, off_sc + sizeof(SampleScalars)));
+    int rc = 0;
+    auto ok = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc == 0) { octa::set_error("octa_sim_kat_sample: %s: %s", what, hipGetErrorString(e)); rc = -1; } return rc == 0; };
+    double *dd = reinterpret_cast<double *>(d);
+    SimArrays A;
+    memset((void *)&A, 0, sizeof(A));
+    A.oxy = dd; A.tmp_dbl = dd + (size_t)OCAP * 3; A.grid_pts = A.tmp_dbl + (size_t)OCAP * 3;
+    double *d_cand = A.grid_pts + (size_t)GRID_N * 3;
+    A.cand = d_cand; A.npos[0] = d_cand + (size_t)NCANDCAP * 3; A.nrad[0] = A.npos[0] + (size_t)NCAP * 3;
+    A.tmp_int = reinterpret_cast<int *>(d + off_int); A.removed = d + off_byte; A.sc = reinterpret_cast<SampleScalars *>(d + off_sc);
+    if (ok(hipMemset(d, 0, off_sc), "clear") && (!n_cand || ok(hipMemcpy(d_cand, h_cand, sizeof(double) * 3 * n_cand, hipMemcpyHostToDevice), "candidates")) &&
+        (!n_art || (ok(hipMemcpy(A.npos[0], h_npos, sizeof(double) * 3 * n_art, hipMemcpyHostToDevice), "nodes") &&
+                    ok(hipMemcpy(A.nrad[0], h_nrad, sizeof(double) * n_art, hipMemcpyHostToDevice), "radii"))) &&
+        (!n_oxy || ok(hipMemcpy(A.oxy, h_oxy, sizeof(double) * 3 * n_oxy, hipMemcpyHostToDevice), "sinks")) &&
+        ok(hipMemcpy(A.sc, &sc, sizeof(sc), hipMemcpyHostToDevice), "scalars") &&
+        ok(hipFuncSetAttribute(reinterpret_cast<const void *>(sim_kat_sample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS), "attribute")) {
+        hipLaunchKernelGGL(sim_kat_sample_kernel, dim3(1), dim3(SIM_THREADS), SIM_LDS, 0, A, C, P);
+        if (ok(hipGetLastError(), "launch") && ok(hipMemcpy(&sc, A.sc, sizeof(sc), hipMemcpyDeviceToHost), "result")) {
+            if (sc.err) { octa::set_error("octa_sim_kat_sample: the phase set error bits %d", sc.err); rc = -3; }
+            else {
+                *h_n_out = sc.n_oxy;
+                const int64_t n = sc.n_oxy < cap_oxy ? sc.n_oxy : cap_oxy;
+                if (n) ok(hipMemcpy(h_oxy, A.oxy, sizeof(double) * 3 * n, hipMemcpyDeviceToHost), "sinks back");
+            }
+        }
+    }
+    (void)hipFree(d);
+    return rc;
+}
 
 #endif
 

@@ -38,6 +38,8 @@ OCTA_DECL(L, octa_simL_impl)
 #undef OCTA_DECL
 int octa_simS_kat_kd_order(octa_ctx *, const double *, int64_t, const uint8_t *, int32_t *);
 int octa_simS_kat_kd_order_signflag(octa_ctx *, const double *, int64_t, const uint8_t *, int32_t, int32_t *);
+int octa_simS_kat_sample(octa_ctx *, const double *, int64_t, const double *, const double *, int64_t, double *, int64_t, int64_t, double, double, double,
+                         const double *, int64_t *);
 }
 
 // Persistent-kernel launches of this process so far, both builds (round 5). A generator that has just finished its own launch waits for the
@@ -138,4 +140,8 @@ extern "C" int octa_sim_fields(octa_sim *sim, int k, double *o, int64_t co, int6
 extern "C" int octa_sim_geometry(int num_cus, int *h_out4) { return octa_simS_geometry(num_cus, h_out4); }
 extern "C" int octa_sim_kat_kd_order(octa_ctx *ctx, const double *p, int64_t n, const uint8_t *need, int32_t *o) { return octa_simS_kat_kd_order(ctx, p, n, need, o); }
 extern "C" int octa_sim_kat_kd_order_signflag(octa_ctx *ctx, const double *p, int64_t n, const uint8_t *need, int32_t bits, int32_t *o) { return octa_simS_kat_kd_order_signflag(ctx, p, n, need, bits, o); }
+extern "C" int octa_sim_kat_sample(octa_ctx *ctx, const double *cand, int64_t n_cand, const double *npos, const double *nrad, int64_t n_art, double *oxy,
+                                   int64_t n_oxy, int64_t cap_oxy, double eps_n, double eps_k, double eps_s, const double *cst8, int64_t *n_out) {
+    return octa_simS_kat_sample(ctx, cand, n_cand, npos, nrad, n_art, oxy, n_oxy, cap_oxy, eps_n, eps_k, eps_s, cst8, n_out);
+}
 extern "C" int octa_sim_is_large(const octa_sim *sim) { return sim && sim->large ? 1 : 0; }

@@ -2179,6 +2179,10 @@ OCTA_HD inline int add_node(const SimArrays &A, int f, V3 p, double r, int paren
 }
 
 // ------------------------------------------------------------------ phase: sample oxygen sinks
+// Two forms. The DIRECT one (the wide-field build, and -DOCTA_SIM_SAMPLE_DIRECT: tests, A/B): the candidates are the queries of two
+// grids built per call over all arterial nodes and all live sinks, their state passes through HBM scratch. The default one further
+// down: the candidates live in the table area for the whole call, binned into ONE small grid, and the nodes and sinks stream past it.
+#if OCTA_SIM_LARGE || defined(OCTA_SIM_SAMPLE_DIRECT)
 OCTA_HD inline void phase_sample(const Blk &b, const SimArrays &A, const SimConst &C, const IterParams &P, int iter) {
     SampleScalars *sc = A.sc;
     const int N = P.N;
@@ -2436,6 +2440,439 @@ OCTA_HD inline void phase_sample(const Blk &b, const SimArrays &A, const SimCons
     SSP(6);
 #undef SSP
 }
+#else
+// The on-chip form. Both tests are existence predicates over fixed sets -- "some sink within eps_s", "some arterial node within
+// min(en, its oxygen distance)" -- so instead of binning the ~3400 nodes and ~4000 sinks per call for 2000 queries, the (at most
+// SMP_CH) candidates of a chunk are binned once: their doubles, cell-ordered, and a live byte per slot stay in the table area; every
+// sink and every node is read once from HBM, coalesced, and clears the live byte of each candidate it rejects (an idempotent store:
+// the order of the clears cannot change a byte). A dead candidate is skipped at its byte, so the pass that runs second sees few. The
+// passers are compacted in candidate order straight into the greedy step's table. Layout of the table area (78 KiB):
+//   [0, 48 K)        pos[SMP_CH][3]   the chunk's valid candidates in cell order          | after the compaction: the greedy step's lists
+//   [48 K, 50 K)     live[SMP_CH]     one byte per slot
+//   [50 K, 74 K)     cell ends, u16 pairs in 32-bit words (LDS atomics are 32-bit)         | after the tests: pp[SMP_GP_MAX][3], the passers
+//   [74 K, 78 K)     slot_of[SMP_CH]  candidate -> slot (0xffff: not valid); the candidate's cell between the two binning passes
+#ifndef OCTA_SIM_SAMPLE_GRID
+#define OCTA_SIM_SAMPLE_GRID 96
+#endif
+#ifndef OCTA_SIM_SAMPLE_NODE_FIRST
+#define OCTA_SIM_SAMPLE_NODE_FIRST 0
+#endif
+constexpr int SMP_CH = 2048;                      // candidates per chunk
+constexpr int SMP_GRID = OCTA_SIM_SAMPLE_GRID;    // cells per axis at most: the cell edge is max(larger query radius, 1.2 / SMP_GRID)
+constexpr int SMP_GP_MAX = 1024, SMP_GPAIR_CAP = 2048;
+constexpr size_t SMP_OFF_LIVE = (size_t)SMP_CH * 24, SMP_OFF_PP = SMP_OFF_LIVE + SMP_CH, SMP_OFF_SLOT = SMP_OFF_PP + (size_t)SMP_GP_MAX * 24;
+static_assert(SMP_CH < 0xffff && SMP_GRID * SMP_GRID < 0xffff, "slots and cells are 16-bit, 0xffff marks a candidate that is not valid");
+static_assert(SMP_OFF_PP + ((size_t)SMP_GRID * SMP_GRID + 2) / 2 * 4 <= SMP_OFF_SLOT && SMP_OFF_SLOT + (size_t)SMP_CH * 2 <= (size_t)SIM_USER_BYTES, "candidate grid layout");
+static_assert((size_t)SMP_GP_MAX * 7 + (size_t)SMP_GPAIR_CAP * 2 <= SMP_OFF_LIVE && (size_t)ACCCAP * 24 <= SMP_OFF_PP + (size_t)SMP_GP_MAX * 24, "greedy acceptance tables");
+// -DOCTA_SIM_SAMPLE_COUNT (host builds; tools/sample_counts.py): what the phase does, summed over the calls -- 0 calls, 1 candidates,
+// 2 valid, 3 arterial nodes, 4 live sinks, 5 / 6 slots the sink pass looks at / finds live, 7 / 8 the same for the node pass,
+// 9 live candidates between the two passes, 10 passers, 11 accepted
+#if defined(OCTA_SIM_SAMPLE_COUNT) && !defined(__HIP_DEVICE_COMPILE__)
+static long smp_count[12];
+static int smp_count_pass = 5;
+#define SMP_COUNT(i, v) (smp_count[i] += (v))
+#else
+#define SMP_COUNT(i, v) ((void)0)
+#endif
+struct SmpGrid {
+    int nc;
+    double x0, inv;
+    unsigned *endw;                // cell c: bits [16 (c & 1), +16) of endw[c >> 1] -- the END of the cell's run of slots
+    const double *pos;
+    unsigned char *live;
+};
+OCTA_HD inline int smp_cell1(const SmpGrid &G, double x) { return grid_clampi((int)floor((x - G.x0) * G.inv), G.nc - 1); }
+OCTA_HD inline int smp_end(const SmpGrid &G, int c) { return (int)((G.endw[c >> 1] >> ((c & 1) * 16)) & 0xffffu); }
+// every LIVE candidate of the cells that [px - radius, px + radius] x [py - radius, py + radius] touches: body(slot, position). A cell
+// row is one run of slots; the bounds of three rows are fetched together.
+template <class F>
+OCTA_HD inline void smp_visit(const SmpGrid &G, double px, double py, double radius, F &&body) {
+    const int cx0 = smp_cell1(G, px - radius), cx1 = smp_cell1(G, px + radius);
+    const int cy0 = smp_cell1(G, py - radius), cy1 = smp_cell1(G, py + radius);
+    for (int cyb = cy0; cyb <= cy1; cyb += 3) {
+        int k0[3], k1[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const int row = cyb + r;
+            k0[r] = k1[r] = 0;
+            if (row <= cy1) {
+                const int c0 = row * G.nc + cx0;
+                k0[r] = c0 ? smp_end(G, c0 - 1) : 0;
+                k1[r] = smp_end(G, row * G.nc + cx1);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            // two slots per step, live byte and position fetched together: one LDS round trip per two candidates instead of two per candidate
+            for (int k = k0[r]; k < k1[r]; k += 2) {
+                const int k2 = k + 1 < k1[r] ? k + 1 : k;
+                const unsigned char l0 = G.live[k], l1 = G.live[k2];
+                const V3 c0 = ld3(G.pos + 3 * k), c1 = ld3(G.pos + 3 * k2);
+                SMP_COUNT(smp_count_pass, 1 + (k2 != k)); SMP_COUNT(smp_count_pass + 1, (l0 != 0) + (l1 && k2 != k));
+                if (l0) body(k, c0);
+                if (l1 && k2 != k) body(k2, c1);
+            }
+        }
+    }
+}
+// The conflict rows of the greedy acceptance, settled in rounds: row j lists the earlier rows within eps_s of it; it is rejected iff one
+// of them is accepted, so it is decided once one listed row is known accepted, or all are known rejected. state[j]: 0 undecided,
+// 1 accepted, 2 rejected (final once set). A row without a list is accepted at once; in every round the first undecided row has only
+// decided rows in front of it, so a round decides at least one row, and by induction over the rows in order every row gets what the
+// serial rule gives it. One wave, a row per lane (its LDS accesses are ordered: no block barrier inside); host build: the same rounds.
+OCTA_HD inline void smp_settle(const Blk &b, int n, const unsigned short *rcnt, const unsigned short *rstart, const unsigned short *pl,
+                               unsigned char *state, unsigned short *crow) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (b.tid >= 64) return;
+    const int lane = b.tid;
+    int n_rows = 0;
+    for (int j0 = 0; j0 < n; j0 += 64) {
+        const bool c = j0 + lane < n && rcnt[j0 + lane] != 0;
+        const unsigned long long m = __ballot(c);
+        if (j0 + lane < n) state[j0 + lane] = c ? 0 : 1;
+        if (c) crow[n_rows + (int)__popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)(j0 + lane);
+        n_rows += (int)__popcll(m);
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+    const int step = 64;
+#else
+    const int lane = 0, step = 1;
+    int n_rows = 0;
+    for (int j = 0; j < n; j++) { state[j] = rcnt[j] ? 0 : 1; if (rcnt[j]) crow[n_rows++] = (unsigned short)j; }
+#endif
+    while (true) {
+        bool left = false;
+        for (int q = lane; q < n_rows; q += step) {
+            const int j = crow[q];
+            if (state[j]) continue;
+            const int s0 = rstart[j], c0 = rcnt[j];
+            bool hit = false, wait = false;
+            for (int k = 0; k < c0; k++) { const int st = state[pl[s0 + k]]; hit |= st == 1; wait |= st == 0; }
+            if (hit) state[j] = 2; else if (!wait) state[j] = 1; else left = true;
+        }
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("" ::: "memory");
+        if (!__any(left)) break;
+#else
+        if (!left) break;
+#endif
+    }
+}
+OCTA_HD inline void phase_sample(const Blk &b, const SimArrays &A, const SimConst &C, const IterParams &P, int iter) {
+    SampleScalars *sc = A.sc;
+    const int N = P.N;
+    const double *cand = A.cand;
+    (void)iter;
+    const double en = fmax(P.eps_n, P.eps_k), es = P.eps_s;
+    const double en2 = en * en;
+    // sqrt is monotone and correctly rounded: outside a relative band of 1e-14 around a squared limit the squared distance decides,
+    // inside it the reference's own expression is evaluated
+    const double es2 = es * es, es2_lo = es2 * (1.0 - 1e-14), es2_hi = es2 * (1.0 + 1e-14);
+    const double GSd = C.gs;
+    const double fcx = C.fc0 * GSd, fcy = C.fc1 * GSd, fr = sc->faz_radius * GSd * 0.5;
+#if defined(OCTA_SIM_PROF_SAMPLE) && defined(__HIP_DEVICE_COMPILE__)
+    // diagnostic build: the kd slots of the phase profile hold this phase's steps: 0 validity + candidate grid, 2 node pass, 4 sink pass,
+    // 5 compaction of the passers, 6 greedy acceptance + append (1 and 3, the direct form's grid builds, stay empty); 7 counts the passers
+    long _st = (long)wall_clock64();
+#define SSP(slot) do { b.sync(); if (b.tid == 0) { long _t = (long)wall_clock64(); sc->kdprof[slot] += _t - _st; _st = _t; } } while (0)
+#else
+#define SSP(slot) do { } while (0)
+#endif
+    unsigned char *const U = b.user_of<2>();
+    double *const pos = reinterpret_cast<double *>(U);
+    unsigned char *const live = U + SMP_OFF_LIVE;
+    unsigned *const endw = reinterpret_cast<unsigned *>(U + SMP_OFF_PP);
+    double *const pp = reinterpret_cast<double *>(U + SMP_OFF_PP);                 // [SMP_GP_MAX][3] the passers' positions
+    unsigned short *const slot_of = reinterpret_cast<unsigned short *>(U + SMP_OFF_SLOT);
+    double *const ppg = A.tmp_dbl;      // the passers in HBM scratch: only for more than one chunk, more than SMP_GP_MAX passers, or a full pair list
+    const int n_art = sc->n_nodes[0];
+    const int n_oxy = sc->n_oxy;
+    const bool single = N <= SMP_CH;
+    SmpGrid G;
+    {
+        const double cell = fmax(fmax(en, es), 1.2 / SMP_GRID);
+        int nc = (int)ceil(1.2 / cell);
+        G.nc = nc < 1 ? 1 : (nc > SMP_GRID ? SMP_GRID : nc);
+        G.x0 = -0.1; G.inv = 1.0 / cell; G.endw = endw; G.pos = pos; G.live = live;
+    }
+    const int nc = G.nc, nwords = (nc * nc + 2) / 2;
+    // the boxes are a hair wider than the radii: a candidate whose ROUNDED distance equals a limit may lie an ulp outside the exact box
+    const double pad = 1e-9;
+    int n_pass = 0;
+    int *ctl = b.coll() + 100;          // [0] accepted (one-wave loop), [1] listed pairs, [2] set when the pair list is full
+    SMP_COUNT(0, 1); SMP_COUNT(1, N); SMP_COUNT(3, n_art); SMP_COUNT(4, n_oxy);
+    if (N <= 0) { b.sync(); if (b.tid == 0) { ctl[0] = 0; ctl[1] = 0; ctl[2] = 0; } }
+    for (int base = 0; base < N; base += SMP_CH) {
+        const int n = N - base < SMP_CH ? N - base : SMP_CH;
+        b.sync();                       // (the table area may still be read: by the phase in front, by the previous chunk's compaction)
+        // 1. is_valid_position (simulation_space.py:89-98) and the counting sort of the valid candidates into the grid
+        for (int w = b.tid; w < nwords; w += b.nth) endw[w] = 0;
+        if (b.tid == 0) { ctl[0] = 0; ctl[1] = 0; ctl[2] = 0; }      // (the greedy step's control words: barriers enough in between)
+        b.sync();
+        for (int i = b.tid; i < n; i += b.nth) {
+            const V3 p = ld3(cand + 3 * (size_t)(base + i));
+            int ok = !(p.x >= C.sx || p.y >= C.sy || p.z >= C.sz || p.x < 0 || p.y < 0 || p.z < 0);
+            if (ok && C.fixed) {
+                // geometry[(pos * geometry_size).astype(np.uint16)] > 0: the candidate came from a valid voxel, but (v + u) / gs * gs may
+                // land one voxel below v
+                const int vi = (int)(unsigned short)(int)(p.x * GSd), vj = (int)(unsigned short)(int)(p.y * GSd), vk = (int)(unsigned short)(int)(p.z * GSd);
+                ok = vi < C.gshape[0] && vj < C.gshape[1] && vk < C.gshape[2] && C.mask[((size_t)vi * C.gshape[1] + vj) * C.gshape[2] + vk] != 0;
+            } else if (ok) {
+                double dd = sqrt((p.x - fcx) * (p.x - fcx) + (p.y - fcy) * (p.y - fcy));
+                ok = dd > fr;
+            }
+            int c = 0xffff;
+            if (ok) {
+                SMP_COUNT(2, 1);
+                c = smp_cell1(G, p.y) * nc + smp_cell1(G, p.x);
+                atomic_add_int(reinterpret_cast<int *>(&endw[c >> 1]), 1 << ((c & 1) * 16));
+            }
+            slot_of[i] = (unsigned short)c;
+        }
+        b.sync();
+        {   // exclusive scan over the cells: a contiguous chunk of words per thread + ONE block scan (a count is at most SMP_CH: no carry)
+            const int chunk = ((nwords + b.nth - 1) / b.nth) | 1;      // odd: distinct LDS banks across the lanes
+            const int w0 = b.tid * chunk < nwords ? b.tid * chunk : nwords, w1 = w0 + chunk < nwords ? w0 + chunk : nwords;
+            int local = 0;
+            for (int w = w0; w < w1; w++) { const unsigned v = endw[w]; local += (int)(v & 0xffffu) + (int)(v >> 16); }
+            int ex;
+            blk_scan(b, local, &ex);
+            unsigned run = (unsigned)ex;
+            for (int w = w0; w < w1; w++) {
+                const unsigned v = endw[w], lo = v & 0xffffu, hi = v >> 16;
+                endw[w] = run | ((run + lo) << 16);
+                run += lo + hi;
+            }
+        }
+        b.sync();
+        for (int i = b.tid; i < n; i += b.nth) {
+            const int c = slot_of[i];
+            if (c != 0xffff) {
+                const V3 p = ld3(cand + 3 * (size_t)(base + i));
+                const int sh = (c & 1) * 16;
+                const int k = (int)(((unsigned)atomic_add_int(reinterpret_cast<int *>(&endw[c >> 1]), 1 << sh) >> sh) & 0xffffu);   // the cell's word ends as its END
+                st3(pos + 3 * k, p);
+                live[k] = 1;
+                slot_of[i] = (unsigned short)k;
+            }
+        }
+        b.sync();
+        SSP(0);
+        // 2. every live sink clears the candidates within eps_s of it (NN <= es), every arterial node those within the ball en AND its
+        //    oxygen distance. No barrier between the two passes: both only clear bytes. Several independent loads per thread in flight.
+        constexpr int SB = 4;
+        auto sink_pass = [&]() {
+            for (int i0 = b.tid; i0 < n_oxy; i0 += SB * b.nth) {
+                V3 s[SB];
+#pragma unroll
+                for (int u = 0; u < SB; u++) { const int i = i0 + u * b.nth; s[u] = ld3(A.oxy + 3 * (size_t)(i < n_oxy ? i : n_oxy - 1)); }
+                OCTA_ISSUE_LOADS();
+#pragma unroll
+                for (int u = 0; u < SB; u++)
+                    if (i0 + u * b.nth < n_oxy)
+                        smp_visit(G, s[u].x, s[u].y, es + pad, [&](int k, const V3 &c) {
+                            const double d2 = sqdist(s[u], c);
+                            if (!(d2 > es2_hi) && (d2 < es2_lo || sqrt(d2) <= es)) live[k] = 0;
+                        });
+            }
+            SSP(4);
+        };
+        auto node_pass = [&]() {
+            for (int i0 = b.tid; i0 < n_art; i0 += SB * b.nth) {
+                V3 q[SB];
+                double rad[SB];
+#pragma unroll
+                for (int u = 0; u < SB; u++) {
+                    const int i = i0 + u * b.nth, ic = i < n_art ? i : n_art - 1;
+                    q[u] = ld3(A.npos[0] + 3 * (size_t)ic);
+                    rad[u] = A.nrad[0][ic];
+                }
+                OCTA_ISSUE_LOADS();
+#pragma unroll
+                for (int u = 0; u < SB; u++)
+                    if (i0 + u * b.nth < n_art) {
+                        const double oxd = oxygen_distance(rad[u], C.ps);
+                        const double lim = oxd < en ? oxd : en;                // (an oxd that is not a number keeps the ball en and fails no comparison below)
+                        const double o2 = oxd * oxd, o2_lo = o2 * (1.0 - 1e-14), o2_hi = o2 * (1.0 + 1e-14);
+                        smp_visit(G, q[u].x, q[u].y, lim + pad, [&](int k, const V3 &c) {
+                            const double d2 = sqdist(q[u], c);
+                            if (d2 <= en2 && !(d2 > o2_hi) && (d2 < o2_lo || !(sqrt(d2) > oxd))) live[k] = 0;
+                        });
+                    }
+            }
+            SSP(2);
+        };
+        for (int rep = 0; rep < ((OCTA_SIM_DUP & 8) ? 2 : 1); rep++) {
+#if defined(OCTA_SIM_SAMPLE_COUNT) && !defined(__HIP_DEVICE_COMPILE__)
+            auto count_live = [&]() { for (int i = 0; i < n; i++) if (slot_of[i] != 0xffff && live[slot_of[i]]) SMP_COUNT(9, 1); };
+            smp_count_pass = OCTA_SIM_SAMPLE_NODE_FIRST ? 7 : 5;
+#if OCTA_SIM_SAMPLE_NODE_FIRST
+            node_pass(); count_live(); smp_count_pass = 5; sink_pass();
+#else
+            sink_pass(); count_live(); smp_count_pass = 7; node_pass();
+#endif
+#elif OCTA_SIM_SAMPLE_NODE_FIRST
+            node_pass(); sink_pass();
+#else
+            sink_pass(); node_pass();
+#endif
+        }
+        b.sync();
+        // 3. the passers, in candidate order, straight into the greedy step's table (the candidates' copy is still there to be read)
+        auto passes = [&](int i) { const int k = slot_of[i]; return k != 0xffff && live[k] != 0; };
+        const int n_cp = ordered_compact(b, n, passes, [&](int i, int at) {
+            const V3 p = ld3(pos + 3 * (int)slot_of[i]);
+            if (single) { if (at < SMP_GP_MAX) st3(pp + 3 * at, p); }
+            else st3(ppg + 3 * (size_t)(n_pass + at), p);
+        });
+        if (single && n_cp > SMP_GP_MAX) {
+            b.sync();
+            ordered_compact(b, n, passes, [&](int i, int at) { st3(ppg + 3 * (size_t)at, ld3(pos + 3 * (int)slot_of[i])); });
+        }
+        n_pass += n_cp;
+    }
+    b.sync();
+    bool in_hbm = !single || n_pass > SMP_GP_MAX;
+    SSP(5);
+#if defined(OCTA_SIM_PROF_SAMPLE) && defined(__HIP_DEVICE_COMPILE__)
+    if (b.tid == 0) sc->kdprof[7] += n_pass;          // (diagnostic build: passers per sample in the last slot)
+#endif
+    // 4. ordered greedy acceptance against the sinks accepted earlier in this call (strict >): candidate j is accepted iff no ACCEPTED
+    //    candidate i < j lies within eps_s. Only candidates that conflict with each other are chained, and those are few (a few dozen
+    //    pairs among the passers). So every pair (i < j) of passers is tested by the whole workgroup (a thread takes the rows j and
+    //    n - 1 - j: n - 1 tests each, the lanes of a wave read the same earlier candidate from the LDS), the conflicting pairs are listed
+    //    per row, smp_settle decides the rows that have any, and an ordered compaction appends the accepted ones: the same set in the
+    //    same order as one candidate after the other.
+    double *acc = reinterpret_cast<double *>(b.user_of<4>());  // [ACCCAP][3] (the one-wave loop only)
+    bool settled = false;
+    int acc_n = 0;
+    if (n_pass <= SMP_GP_MAX) {
+        unsigned short *rcnt = reinterpret_cast<unsigned short *>(U);    // [SMP_GP_MAX] conflicts of row j with rows before it
+        unsigned short *rstart = rcnt + SMP_GP_MAX;                      // [SMP_GP_MAX] where they are listed
+        unsigned short *crow = rstart + SMP_GP_MAX;                      // [SMP_GP_MAX] the rows that have any
+        unsigned short *pl = crow + SMP_GP_MAX;                          // [SMP_GPAIR_CAP] the earlier rows, row by row
+        unsigned char *state = reinterpret_cast<unsigned char *>(pl + SMP_GPAIR_CAP);   // [SMP_GP_MAX] smp_settle
+        if (!single) {
+            for (int j = b.tid; j < 3 * n_pass; j += b.nth) pp[j] = ppg[j];
+            b.sync();
+        }
+        auto conflicts = [&](const V3 &c, int i) {
+            const V3 d = sub(c, ld3(pp + 3 * i));
+            const double s2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+            if (s2 > es2_hi) return false;
+            if (s2 < es2_lo) return true;
+            return !(sqrt(s2) > es);
+        };
+        for (int t = b.tid; 2 * t < n_pass; t += b.nth) {
+            for (int side = 0; side < 2; side++) {
+                const int j = side == 0 ? t : n_pass - 1 - t;
+                if (side == 1 && j == t) break;
+                const V3 c = ld3(pp + 3 * j);
+                int cnt = 0;
+                int f0 = 0, f1 = 0;       // the row's first two conflicts stay in registers: a row seldom has more, and then nothing is tested twice
+#define SMP_HIT(i_) do { if (cnt == 0) f0 = (i_); else if (cnt == 1) f1 = (i_); cnt++; } while (0)
+                {   // eight earlier candidates per step, their positions fetched together: the loop is a chain of LDS round trips otherwise
+                    int i = 0;
+                    for (; i + 8 <= j; i += 8) {
+                        V3 a[8];
+#pragma unroll
+                        for (int u = 0; u < 8; u++) a[u] = ld3(pp + 3 * (i + u));
+#pragma unroll
+                        for (int u = 0; u < 8; u++) {
+                            const V3 d = sub(c, a[u]);
+                            const double s2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+                            if (!(s2 > es2_hi) && (s2 < es2_lo || !(sqrt(s2) > es))) SMP_HIT(i + u);
+                        }
+                    }
+                    for (; i < j; i++) if (conflicts(c, i)) SMP_HIT(i);
+                }
+#undef SMP_HIT
+                int listed = 0;           // (every row's count is written by the thread that owns the row: no pass that clears them)
+                if (cnt > 0) {
+                    const int at = atomic_add_int(&ctl[1], cnt);
+                    if (at + cnt <= SMP_GPAIR_CAP) {
+                        if (cnt <= 2) { pl[at] = (unsigned short)f0; if (cnt == 2) pl[at + 1] = (unsigned short)f1; }
+                        else { int w = at; for (int i = 0; i < j; i++) if (conflicts(c, i)) pl[w++] = (unsigned short)i; }
+                        rstart[j] = (unsigned short)at; listed = cnt;
+                    } else {
+                        ctl[2] = 1;
+                    }
+                }
+                rcnt[j] = (unsigned short)listed;
+            }
+        }
+        b.sync();
+        if (OCTA_UNI(ctl[2]) == 0) {
+            settled = true;
+            smp_settle(b, n_pass, rcnt, rstart, pl, state, crow);
+            b.sync();
+            const int room = OCAP - n_oxy < ACCCAP ? OCAP - n_oxy : ACCCAP;
+            const int acc_all = ordered_compact(b, n_pass, [&](int q) { return state[q] == 1; },
+                                                [&](int q, int at) { if (at < room) st3(A.oxy + 3 * (size_t)(n_oxy + at), ld3(pp + 3 * q)); });
+            if (acc_all > ACCCAP && b.tid == 0) atomic_or_int(&sc->err, ERR_ACC_CAP);
+            acc_n = acc_all < ACCCAP ? acc_all : ACCCAP;          // (the block total: every thread holds it)
+        } else if (!in_hbm) {
+            for (int j = b.tid; j < 3 * n_pass; j += b.nth) ppg[j] = pp[j];
+            in_hbm = true;
+        }
+    }
+    if (!settled) {
+        // the pair list overflowed, or more passers than the table holds: one candidate after the other against the accepted ones
+        b.sync();
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (b.tid < 64) {
+            const int lane = b.tid;
+            int an = 0;
+            for (int q0 = 0; q0 < n_pass; q0 += 64) {
+                // the next 64 candidates, one per lane: one memory round trip per 64 candidates
+                V3 mine = v3(0, 0, 0);
+                if (q0 + lane < n_pass) mine = ld3(ppg + 3 * (size_t)(q0 + lane));
+                const int cnt = n_pass - q0 < 64 ? n_pass - q0 : 64;
+                for (int jj = 0; jj < cnt; jj++) {
+                    const int jl = __builtin_amdgcn_readfirstlane(jj);
+                    const V3 c = v3(readlane_f64(mine.x, jl), readlane_f64(mine.y, jl), readlane_f64(mine.z, jl));
+                    bool conflict = false;
+                    for (int j = lane; j < an; j += 64)
+                        if (!(rownorm(sub(c, ld3(acc + 3 * j))) > es)) conflict = true;
+                    if (!__any(conflict)) {
+                        if (an < ACCCAP) { if (lane == 0) st3(acc + 3 * an, c); }
+                        else if (lane == 0) atomic_or_int(&sc->err, ERR_ACC_CAP);
+                        an++;
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                }
+            }
+            if (lane == 0) ctl[0] = an < ACCCAP ? an : ACCCAP;
+        }
+#else
+        int an = 0;
+        for (int q = 0; q < n_pass; q++) {
+            const V3 c = ld3(ppg + 3 * (size_t)q);
+            bool conflict = false;
+            for (int j = 0; j < an && j < ACCCAP; j++)
+                if (!(rownorm(sub(c, ld3(acc + 3 * j))) > es)) { conflict = true; break; }
+            if (!conflict) {
+                if (an < ACCCAP) st3(acc + 3 * an, c); else atomic_or_int(&sc->err, ERR_ACC_CAP);
+                an++;
+            }
+        }
+        ctl[0] = an < ACCCAP ? an : ACCCAP;
+#endif
+        b.sync();
+        acc_n = ctl[0];
+    }
+    if (n_oxy + acc_n > OCAP) { if (b.tid == 0) atomic_or_int(&sc->err, ERR_OXY_CAP); acc_n = OCAP - n_oxy; }
+    if (!settled)
+        for (int j = b.tid; j < acc_n * 3; j += b.nth) A.oxy[3 * n_oxy + j] = acc[j];
+    if (b.tid == 0) sc->n_oxy = n_oxy + acc_n;
+    SMP_COUNT(10, n_pass); SMP_COUNT(11, acc_n);
+    b.sync();
+    SSP(6);
+#undef SSP
+}
+#endif
 
 // ------------------------------------------------------------------ phase: nearest active node + dict order
 constexpr int ASSIGN_STAGE = 256;      // nodes created since the forest's previous assignment that phase_assign tests per attractor (more: grid scan for all)
