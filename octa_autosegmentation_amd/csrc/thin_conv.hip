@@ -456,8 +456,10 @@ lrelu_bwd_kernel(const bf16_t *__restrict__ y, const bf16_t *__restrict__ dy, bf
     }
 }
 
-bool shape_ok(const char *fn, int N, int H, int W, int C, int K, int pad) {
-    if (N <= 0 || H <= 0 || W <= 0 || (K != 4 && K != 7) || pad < 0 || pad >= K || H + 2 * pad < K || W + 2 * pad < K) {
+// window: H x W is the INPUT of a convolution (expand, squeeze), which has to hold one K x K window. wgrad's H x W is the extent of `a`, the
+// side the window slides over: any extent is a sum (a 1 x Wo output gradient at pad 0 is the weight gradient of an H = K image).
+bool shape_ok(const char *fn, int N, int H, int W, int C, int K, int pad, bool window = true) {
+    if (N <= 0 || H <= 0 || W <= 0 || (K != 4 && K != 7) || pad < 0 || pad >= K || (window && (H + 2 * pad < K || W + 2 * pad < K))) {
         octa::set_error("%s: unsupported shape (N %d, H %d, W %d, K %d, pad %d; K is 4 or 7)", fn, N, H, W, K, pad);
         return false;
     }
@@ -545,7 +547,7 @@ extern "C" long long octa_thinconv_wgrad_scratch_floats(int N, int Ha, int C, in
 extern "C" int octa_thinconv_wgrad(octa_ctx *ctx, const void *d_a, const void *d_s, void *d_scratch, void *d_g, void *d_asum, int N, int Ha, int Wa,
                                    int Hs, int Ws, int C, int K, int pad, int flip, void *stream_) {
     if (!ctx || !d_a || !d_s || !d_scratch || !d_g) { octa::set_error("octa_thinconv_wgrad: null argument"); return -2; }
-    if (!shape_ok("octa_thinconv_wgrad", N, Ha, Wa, C, K, pad)) return -2;
+    if (!shape_ok("octa_thinconv_wgrad", N, Ha, Wa, C, K, pad, false)) return -2;
     if (Hs <= 0 || Ws <= 0) { octa::set_error("octa_thinconv_wgrad: bad s extent"); return -2; }
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_;
