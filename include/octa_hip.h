@@ -562,6 +562,19 @@ int octa_blur_up_bwd(octa_ctx *ctx, const void *d_in, void *d_out, int dtype, in
 int octa_remove_small_objects(octa_ctx *ctx, const uint8_t *d_in, int B, int H, int W, int min_size, int connectivity,
                               uint8_t on_value, uint8_t *d_out, void *stream);
 
+/* 3-D connected components for the volume post-processing (reference RemoveOuterNoise / MONAI's
+ * KeepLargestConnectedComponent and a volume-wise RemoveSmallObjects): d_in, d_out uint8 [B][D][H][W] (non-zero = foreground;
+ * d_out must not overlap d_in). connectivity 1 / 2 / 3 = the 6- / 18- / 26-neighbourhood; with D == 1 this is the 2-D case
+ * (1 / 2 = 4- / 8-neighbourhood, 3 behaves as 2). mode 0: a component with at least min_size voxels survives; mode 1: the
+ * component with the most voxels of each volume survives (min_size unused), on a tie the one whose first voxel comes first in C
+ * order -- argmax(bincount(labels)[1:]) + 1 on raster-ordered labels. Survivors get on_value, everything else 0; a volume without
+ * foreground gives zeros. Volumes of a batch are never united. d_info (device, may be NULL): int64 [B][3] = number of components,
+ * voxels of the largest, flat index inside the volume of its first voxel (-1 if there is none). Integer work only: the output is
+ * the same on every run. -2: bad pointers, a non-positive size, connectivity outside 1..3, mode outside 0..1, more than
+ * 2^31 - 1 voxels in the batch. */
+int octa_cc3d_filter(octa_ctx *ctx, const uint8_t *d_in, int B, int D, int H, int W, int connectivity, int mode, int min_size,
+                     uint8_t on_value, uint8_t *d_out, int64_t *d_info, void *stream);
+
 /* ---- skeletonisation for the clDice metric --------------
  * Zhang & Suen's 1984 parallel thinning (what skimage.morphology.skeletonize does in 2-D; reference utils/cldice.py) of a batch of
  * masks in HBM: d_in uint8 [B][H][W] (non-zero = foreground, outside the image = background), d_out uint8 [B][H][W] = 0 / 1, the

@@ -10,7 +10,7 @@ Two groups:
   model NoiseModeld with RandomDecreaseResolutiond (:435-496);
 * the MONAI transforms those configs name (LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, RandFlipd, RandRotate90d,
   RandRotated, Rotate90d, Flipd, AsDiscreted, CastToTyped; post-processing: Activations, AsDiscrete, RemoveSmallObjects,
-  CastToType), restated from MONAI's documented behaviour. MONAI is neither in the image nor under /root/reference:
+  KeepLargestConnectedComponent, CastToType; RemoveOuterNoise is the reference's own, :418-432), restated from MONAI's documented behaviour. MONAI is neither in the image nor under /root/reference:
   parity with MONAI itself -- in particular its per-transform random streams -- is UNPINNED; the geometry is pinned against
   the torch ops MONAI delegates to (tests/test_augment_gpu.py, tests/test_data_pipeline.py).
 """
@@ -898,17 +898,62 @@ class AsDiscrete:
 class RemoveSmallObjects:
     """Connected components smaller than min_size removed (MONAI -> skimage.morphology.remove_small_objects; connectivity 1
     = 4-neighbourhood). On the GPU through the union-find kernel of csrc/postproc.hip, bit-exact with scipy.ndimage.label +
-    bincount (tests/test_postproc_gpu.py)."""
+    bincount (tests/test_postproc_gpu.py). independent_channels=False (MONAI's keyword): the leading axis of a [C,H,W] input is
+    depth and the components are those of the volume (csrc/cc3d.hip; connectivity 1 / 2 / 3 = 6- / 18- / 26-neighbourhood)."""
 
-    def __init__(self, min_size=64, connectivity=1, **unused):
-        self.min_size, self.connectivity = int(min_size), int(connectivity)
+    def __init__(self, min_size=64, connectivity=1, independent_channels=True, **unused):
+        self.min_size, self.connectivity, self.independent_channels = int(min_size), int(connectivity), bool(independent_channels)
 
     def __call__(self, x):
         from ..models.postprocess import remove_small_objects_device
         if not x.is_cuda:
             raise RuntimeError("RemoveSmallObjects runs on the GPU (no CPU fallback)")
-        keep = remove_small_objects_device((x != 0).to(torch.uint8), self.min_size, self.connectivity)
+        keep = remove_small_objects_device((x != 0).to(torch.uint8), self.min_size, self.connectivity, independent_channels=self.independent_channels)
         return x * keep.to(x.dtype)
+
+
+class KeepLargestConnectedComponent:
+    """MONAI's KeepLargestConnectedComponent for ONE foreground label: input [1, *spatial] with 2 or 3 spatial dims, non-zero =
+    foreground; everything outside the component with the most voxels is zeroed, dtype kept. A tie goes to the component whose first
+    voxel comes first in C order (argmax(bincount(labels)[1:]) + 1 on skimage's raster-ordered labels). connectivity None = full.
+    MONAI treats several non-zero values of a one-channel image as separate labels and keeps the largest component of each; this
+    class does not: every non-zero value is the same foreground. applied_labels, is_onehot=True, independent=False,
+    num_components != 1 and more than one channel raise NotImplementedError. GPU only (csrc/cc3d.hip)."""
+
+    def __init__(self, applied_labels=None, is_onehot=None, independent=True, connectivity=None, num_components=1):
+        for arg, bad in (("applied_labels", applied_labels is not None), ("is_onehot", bool(is_onehot)), ("independent", not independent),
+                         ("num_components", num_components != 1)):
+            if bad:
+                raise NotImplementedError(f"KeepLargestConnectedComponent: {arg} is supported only at its default (one foreground label, one component)")
+        self.connectivity = None if connectivity is None else int(connectivity)
+
+    def __call__(self, x):
+        from ..models.postprocess import keep_largest_component_device
+        if not x.is_cuda:
+            raise RuntimeError("KeepLargestConnectedComponent runs on the GPU (no CPU fallback)")
+        if x.dim() not in (3, 4):
+            raise NotImplementedError(f"KeepLargestConnectedComponent: the input must be [1, *spatial] with 2 or 3 spatial dims, got {tuple(x.shape)}")
+        if x.shape[0] != 1:
+            raise NotImplementedError(f"KeepLargestConnectedComponent: is_onehot / several channels ({x.shape[0]}) are not supported")
+        keep = keep_largest_component_device(x[0], self.connectivity)
+        return x * keep[None].to(x.dtype)
+
+
+class RemoveOuterNoise:
+    """The reference's RemoveOuterNoise (data/data_transforms.py:418-432): everything of a volume that is not 26-connected to its
+    central plane goes. Literally: a boolean copy, plane `volume.shape[z_axis] // 2` OF DIM 0 filled (the reference indexes dim 0
+    whatever z_axis is -- kept, so z_axis only picks the length that is halved, and an index past dim 0 raises IndexError as there),
+    the largest 26-connected component of that (KeepLargestConnectedComponent), logical_and with the input. Returns torch.bool.
+    GPU only (csrc/cc3d.hip)."""
+
+    def __init__(self, z_axis=0, **unused):
+        self.z_axis = int(z_axis)
+
+    def __call__(self, volume):
+        from ..models.postprocess import remove_outer_noise_device
+        if not volume.is_cuda:
+            raise RuntimeError("RemoveOuterNoise runs on the GPU (no CPU fallback)")
+        return remove_outer_noise_device(volume, self.z_axis)
 
 
 class CastToType:
@@ -933,7 +978,8 @@ TRANSFORMS = {c.__name__: c for c in (
     LoadGraphAndFilterByRandomRadiusd, ToGrayScaled, SpeckleBrightnesd, AddRandomBackgroundNoised, ImageToImageTranslationd,
     BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact, MentenAugmentationd, NoiseModeld, RandomDecreaseResolutiond,
     LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, Flipd, RandFlipd, Rotate90d, RandRotate90d, RandRotated, AsDiscreted,
-    CastToTyped, SelectSlice, Activations, AsDiscrete, RemoveSmallObjects, Resize, CastToType, AsChannelLast)}
+    CastToTyped, SelectSlice, Activations, AsDiscrete, RemoveSmallObjects, KeepLargestConnectedComponent, RemoveOuterNoise, Resize, CastToType,
+    AsChannelLast)}
 
 
 def get_data_augmentations(aug_config, seed=None, dtype=torch.float32):
