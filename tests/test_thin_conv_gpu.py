@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _thin_ref as tr
+from _guarded import DEV, Guarded      # the sentinel-filled buffers, shared with tests/test_conv_exact_gpu.py
 
 pytestmark = pytest.mark.gpu
 
@@ -98,27 +99,6 @@ def test_lrelu_backward_kernel_equals_the_torch_expression(hip_lib_built):
 
 
 # ---- the kernels against tests/_thin_ref.py ---------------------------------------------------------------------------------------------
-
-DEV = "cuda"
-GUARD = 1024                                   # elements of sentinel in front of and behind every buffer a kernel writes
-SENT = {torch.bfloat16: (torch.int16, 0x5A5B), torch.float32: (torch.int32, 0x5A5B5C5D)}     # as values: 1.5e16 (bf16 and fp32)
-
-
-class Guarded:
-    """A tensor a kernel writes, inside a larger buffer whose head, tail AND body hold a sentinel bit pattern: a store outside the tensor
-    changes head or tail, an element the kernel never stores keeps a value no case produces."""
-
-    def __init__(self, shape, dtype):
-        self.n = 1
-        for d in shape:
-            self.n *= int(d)
-        it, self.pattern = SENT[dtype]
-        self.raw = torch.full((2 * GUARD + self.n,), self.pattern, dtype=it, device=DEV)
-        self.t = self.raw[GUARD:GUARD + self.n].view(dtype).view(tuple(shape))
-
-    def intact(self):
-        return bool((self.raw[:GUARD] == self.pattern).all()) and bool((self.raw[GUARD + self.n:] == self.pattern).all())
-
 
 def _dev(ops):
     return {k: (v.to(DEV) if v is not None else None) for k, v in ops.items()}
