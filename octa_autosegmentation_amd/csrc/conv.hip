@@ -7,7 +7,9 @@
 // NCHW<->NHWC transposes around its implicit-GEMM kernels (14 % of the step, profiles/r01_train_kernel_stats.csv);
 // here the activations stay NHWC end to end.
 //
-// Implicit GEMM, one 256-thread workgroup per 8 x 32 output-pixel tile and BN output channels:
+// The default forward / data-gradient kernel is the DMA-staged conv3x3_nhwc_glds_kernel; the register-staged conv3x3_nhwc_kernel
+// described next is the normalise-on-load path and runs only when scale / shift operands are given. Both share tile and MFMA layout:
+// implicit GEMM, one 256-thread workgroup per 8 x 32 output-pixel tile and BN output channels:
 //   * per 32-channel slice of the input: the (8*st+2) x (32*st+2) halo tile is staged once in LDS
 //     ([y][x][32 ch], 80-byte pixel pitch: a 16-lane ds_read_b128 group then touches all 64 banks once) and
 //     reused by the nine taps; the weight slice [9][BN][32] is staged beside it (same pitch);
@@ -54,8 +56,9 @@ __device__ __forceinline__ unsigned short f2bf(float f) { return octa_f2bf(f); }
 // X: [N][H][W][Cin] (bf16 bits), Wt: [9][Cout][Cin], Y: [N][Ho][Wo][Cout].
 // out(y, x) = sum_{r,s,ci} Xv(y*st + r - 1, x*st + s - 1, ci) * Wt[3r+s][co][ci], where the virtual input is
 // Xv(yy, xx) = X[yy/dil][xx/dil] if 0 <= yy < H*dil, 0 <= xx < W*dil and yy, xx multiples of dil, else 0.
-// EXTRA = false compiles the plain kernel; true adds normalise-on-load and the statistics epilogue (both measured
-// slower in the U-Net step, kept for experiments -- as a template flag they cost the plain kernel nothing).
+// Two forward kernels: conv3x3_nhwc_glds_kernel (DMA-staged: operands go HBM -> LDS without passing registers) is the default;
+// conv3x3_nhwc_kernel (register-staged, right below) is the normalise-on-load path -- it runs when scale / shift operands are
+// given, because only a staging pass through registers can transform the input on its way into LDS.
 // ---- packed weights: SLICE-MAJOR storage (round 5) ------------------------------------------------------------------------------
 // Every kernel below reads its weights 16 input channels at a time (one K-step of v_mfma_f32_32x32x16_bf16) for all taps and a block of
 // output channels. Rounds 1-4 kept them tap-major, [KK][Cout][Cin] with Cin fastest: a 16-channel slice of a row is then 32 bytes out
@@ -68,7 +71,7 @@ __host__ __device__ __forceinline__ size_t wt_off(int t, int co, int ci, int KK,
     return (((size_t)(ci >> 4) * KK + t) * Cout + co) * 16 + (ci & 15);
 }
 
-template <int BN, int ST, bool EXTRA, bool MASKED>
+template <int BN, int ST>
 __global__ void __launch_bounds__(CONV_THREADS)
 conv3x3_nhwc_kernel(const unsigned short *__restrict__ X, const unsigned short *__restrict__ X2, int C1,
                     const unsigned short *__restrict__ Wt, unsigned short *__restrict__ Y, unsigned short *__restrict__ Y2, int CY1,
@@ -104,7 +107,7 @@ conv3x3_nhwc_kernel(const unsigned short *__restrict__ X, const unsigned short *
         // lrelu(x * scale + shift) (InstanceNorm affine + LeakyReLU, per image and channel) while it is staged, rounded
         // to bf16 exactly like the materialised tensor would have been; padding stays zero.
         const float *scp = c0 < C1 ? sc1 : sc2, *shp = c0 < C1 ? sh1 : sh2;
-        const bool xform = EXTRA && scp != nullptr;
+        const bool xform = scp != nullptr;
         if (xform) {
             if (threadIdx.x < KC) s_ss[threadIdx.x] = scp[(size_t)n * cs + cb + threadIdx.x];
             else if (threadIdx.x < 2 * KC) s_ss[threadIdx.x] = shp[(size_t)n * cs + cb + threadIdx.x - KC];
@@ -139,7 +142,7 @@ conv3x3_nhwc_kernel(const unsigned short *__restrict__ X, const unsigned short *
         for (int i = threadIdx.x; i < 9 * BN * 4; i += CONV_THREADS) {
             const int row = i >> 2, q = i & 3;
             const int tap = row / BN, co = row % BN;
-            if (MASKED && !((tap_mask >> tap) & 1)) continue;   // unused taps are neither staged nor multiplied
+            if (!((tap_mask >> tap) & 1)) continue;   // unused taps are neither staged nor multiplied
             const uint4 v = *reinterpret_cast<const uint4 *>(Wt + wt_off(tap, co0 + co, c0 + q * 8, 9, Cout));
             *reinterpret_cast<uint4 *>(s_w + row * PITCH + q * 16) = v;
         }
@@ -148,7 +151,7 @@ conv3x3_nhwc_kernel(const unsigned short *__restrict__ X, const unsigned short *
         for (int r = 0; r < 3; r++)
 #pragma unroll
             for (int s = 0; s < 3; s++) {
-                if (MASKED && !((tap_mask >> (3 * r + s)) & 1)) continue;   // taps whose weights are structurally zero
+                if (!((tap_mask >> (3 * r + s)) & 1)) continue;   // taps whose weights are structurally zero
 #pragma unroll
                 for (int ks = 0; ks < KC / 16; ks++) {
                     bf16x8 a[2], b[NB];
@@ -174,33 +177,7 @@ conv3x3_nhwc_kernel(const unsigned short *__restrict__ X, const unsigned short *
     // larger (osc = 2: one parity class of a zero-insertion-free stride-2 data gradient / 2x2 transposed convolution).
     unsigned short *Yo = co0 < CY1 ? Y : Y2;
     const int ys = co0 < CY1 ? CY1 : Cout - CY1, yb = co0 < CY1 ? co0 : co0 - CY1;
-    if (!EXTRA) { osc = 1; ooy = 0; oox = 0; }   // the scattered store is compiled into the EXTRA variant only
     const int HoF = Ho * osc, WoF = Wo * osc;
-    if (!EXTRA) {
-        // Coalesced store: the tile goes through LDS ([pixel][BN channels], 16-byte padded rows) so that consecutive
-        // threads write consecutive 16-byte pieces -- whole 64/128-byte pixel rows, whole tile rows back to back --
-        // instead of 2-byte elements 64 bytes apart.
-        constexpr int OP = BN * 2 + 16;                 // bytes per pixel row in LDS
-        unsigned char *s_out = smem;                    // [TH*TW] rows; the operand tiles are dead now
-        __syncthreads();
-#pragma unroll
-        for (int rr = 0; rr < 2; rr++)
-#pragma unroll
-            for (int nb = 0; nb < NB; nb++)
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int px = (k & 3) + 8 * (k >> 2) + 4 * kg;
-                    *reinterpret_cast<unsigned short *>(s_out + ((2 * wv + rr) * TW + px) * OP + (nb * 32 + m) * 2) = f2bf(acc[rr][nb][k]);
-                }
-        __syncthreads();
-        constexpr int PIECES = BN / 8;                  // 16-byte pieces per pixel
-        for (int i = threadIdx.x; i < TH * TW * PIECES; i += CONV_THREADS) {
-            const int p = i / PIECES, q = i % PIECES;
-            const int oy = ty0 + p / TW, ox = tx0 + p % TW;
-            if (oy < Ho && ox < Wo)
-                *reinterpret_cast<uint4 *>(Yo + (((size_t)n * Ho + oy) * Wo + ox) * ys + yb + q * 8) = *reinterpret_cast<const uint4 *>(s_out + p * OP + q * 16);
-        }
-    } else {
 #pragma unroll
     for (int rr = 0; rr < 2; rr++) {
         const int oy = ty0 + 2 * wv + rr;
@@ -213,10 +190,9 @@ conv3x3_nhwc_kernel(const unsigned short *__restrict__ X, const unsigned short *
                 if (ox < Wo) Yo[(((size_t)n * HoF + oy * osc + ooy) * WoF + ox * osc + oox) * ys + yb + nb * 32 + m] = f2bf(acc[rr][nb][k]);
             }
     }
-    }
     // InstanceNorm statistics of the layer that follows, for free: per tile and output channel the sum and the sum of
     // squares of the bf16-ROUNDED results (what the norm kernels would read back) -> part[n][tile][Cout][2]
-    if (EXTRA && part) {
+    if (part) {
         float s1[NB], s2[NB];
 #pragma unroll
         for (int nb = 0; nb < NB; nb++) { s1[nb] = 0.f; s2[nb] = 0.f; }
@@ -252,33 +228,50 @@ conv3x3_nhwc_kernel(const unsigned short *__restrict__ X, const unsigned short *
     }
 }
 
-template <int BN, int ST, bool EXTRA, bool MASKED>
-int launch_conv_impl(const unsigned short *X, const unsigned short *X2, int C1, const unsigned short *Wt, unsigned short *Y, unsigned short *Y2,
-                int CY1, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int dil, int tap_mask, int osc, int ooy, int oox,
-                const float *sc1, const float *sh1, const float *sc2, const float *sh2, float slope, float *part, hipStream_t stream) {
+// One forward launch, filled by the entry point after its checks: operands, extents and options of every forward launcher below
+// (a launcher reads what its kernel takes; what an entry point does not offer stays at the neutral value given here).
+struct FwdLaunch {
+    const unsigned short *X = nullptr, *X2 = nullptr, *Wt = nullptr;     // X2: the second input of a virtual concatenation (channels C1 .. Cin)
+    unsigned short *Y = nullptr, *Y2 = nullptr;      // Y2: the second output of a split (channels CY1 .. Cout)
+    int C1 = 0, CY1 = 0, N = 0, H = 0, W = 0, Cin = 0, Ho = 0, Wo = 0, Cout = 0, dil = 1;
+    int tap_mask = 0, osc = 1, ooy = 0, oox = 0;      // taps to evaluate; parity scatter of the output
+    int pad = 1, reflect = 0;
+    const float *sc1 = nullptr, *sh1 = nullptr, *sc2 = nullptr, *sh2 = nullptr;   // normalise-on-load (register-staged kernel only)
+    float slope = 0.f;
+    float *part = nullptr;                           // statistics: per-tile partials, or double slots when nslot > 0
+    int nslot = 0;
+    const unsigned short *R = nullptr;               // residual
+    const unsigned short *zero16 = nullptr;          // zero page (DMA-staged kernels)
+    hipStream_t stream = nullptr;
+};
+
+template <int BN, int ST>
+int launch_conv(const FwdLaunch &L) {
     constexpr int IH = (TH - 1) * ST + 3, IW = (TW - 1) * ST + 3;
     const size_t lds = (size_t)IH * IW * PITCH + (size_t)9 * BN * PITCH + 2 * KC * sizeof(float);
-    const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + TH - 1) / TH;
-    auto kern = conv3x3_nhwc_kernel<BN, ST, EXTRA, MASKED>;
+    const int tiles_x = (L.Wo + TW - 1) / TW, tiles_y = (L.Ho + TH - 1) / TH;
+    auto kern = conv3x3_nhwc_kernel<BN, ST>;
     OCTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(Cout / BN), (unsigned)N);
-    hipLaunchKernelGGL(kern, grid, dim3(CONV_THREADS), lds, stream, X, X2, C1, Wt, Y, Y2, CY1, H, W, Cin, Ho, Wo, Cout, dil, tiles_x, tap_mask, osc, ooy, oox,
-                       sc1, sh1, sc2, sh2, slope, part);
+    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(L.Cout / BN), (unsigned)L.N);
+    hipLaunchKernelGGL(kern, grid, dim3(CONV_THREADS), lds, L.stream, L.X, L.X2, L.C1, L.Wt, L.Y, L.Y2, L.CY1, L.H, L.W, L.Cin, L.Ho, L.Wo, L.Cout, L.dil,
+                       tiles_x, L.tap_mask, L.osc, L.ooy, L.oox, L.sc1, L.sh1, L.sc2, L.sh2, L.slope, L.part);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 // ---- stride-1 kernel with asynchronous global -> LDS staging (global_load_lds, 16 bytes per lane) -------------------------
-// Same tile, same MFMA schedule and same epilogue as conv3x3_nhwc_kernel<BN, 1, false, false>, but the operand slices
+// Same tile and same MFMA operands as conv3x3_nhwc_kernel<BN, 1>, but the operand slices (KCV = 16 channels each)
 // never pass through VGPRs: every wave issues global_load_lds_dwordx4 for the NEXT slice into the other LDS buffer, then
 // multiplies the current one, so the HBM/L2 latency of a slice hides under the 72 (BN = 64) MFMAs of the previous slice
 // and the ds_write_b128 pass (~79 B/clk/CU) disappears. One barrier per slice.
 // The DMA writes LDS lane-linearly (wave-uniform base + lane * 16), so the LDS image is an unpadded array of 16-byte
-// pieces [row][PP] (row = halo pixel or weight row, PP = KCV / 8 pieces) and the bank spread comes from an XOR swizzle
-// applied to BOTH the source address and the read: piece q of row p lives in slot p * PP + (q ^ swz(p)), swz(p) =
-// (p >> 2) & 3 for PP = 4: the 16 rows of one ds_read_b128 lane group then cover all 64 banks once.
+// pieces [row][PP] (row = halo pixel or weight row, PP = KCV / 8 = 2 pieces, 32 bytes per row) and the bank spread comes from
+// an XOR swizzle applied to BOTH the source address and the read: piece q of row p lives in slot p * PP + (q ^ swz(p)), swz(p) =
+// (p >> 3) & 1: of the 16 rows of one ds_read_b128 lane group eight read one half of their row and eight the other half, and the
+// group covers all 64 banks once.
 // Out-of-image halo pixels (padding, the zero rows of a virtual zero insertion) are fetched from a 16-byte zero page.
-template <int PP> __device__ __forceinline__ int glds_swz(int p) { return PP == 4 ? (p >> 2) & 3 : (p >> 3) & 1; }
+constexpr int KCV = 16, PP = KCV / 8;      // input channels per DMA-staged slice (one K-step of the MFMA); 16-byte pieces per LDS row
+__device__ __forceinline__ int glds_swz(int p) { return (p >> 3) & 1; }
 
 __device__ __forceinline__ void glds16(const void *gsrc, unsigned char *lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
@@ -289,7 +282,7 @@ __device__ __forceinline__ void glds16(const void *gsrc, unsigned char *lds_wave
 // column, so the LDS image keeps the even and the odd halo columns of a row in two planes ([row][parity][33 pixels]):
 // the 32 lanes of a tap then read 32 CONSECUTIVE LDS pixels again and the swizzle stays conflict-free. One workgroup
 // per CU (2 x 54 KB of LDS), the loads of the next slice still overlap the MFMAs of the current one.
-template <int BN, int KCV, bool STATS, bool MASKED, int ST, int KS, int THT>
+template <int BN, bool STATS, bool MASKED, int ST, int KS, int THT>
 __global__ void __launch_bounds__(CONV_THREADS, (THT == 16 ? 2 : 1))
 conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned short *__restrict__ X2, int C1,
                          const unsigned short *__restrict__ Wt, unsigned short *__restrict__ Y, unsigned short *__restrict__ Y2, int CY1,
@@ -300,7 +293,7 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
     constexpr int IH = (THT - 1) * ST + KS, IW = (TW - 1) * ST + KS;   // KS x KS taps (3: the U-Net / generator layers, 4: the PatchGAN)
     constexpr int PW = (IW + ST - 1) / ST;                 // pixels per LDS plane row (ST = 2: 33 even / 32 odd columns)
     constexpr int LPIX = IH * ST * PW;                      // pixels of the LDS image
-    constexpr int PP = KCV / 8, NB = BN / 32;
+    constexpr int NB = BN / 32;
     constexpr int IN_INSTR = (LPIX * PP + 63) / 64, W_INSTR = KS * KS * BN * PP / 64;
     constexpr int IN_BYTES = IN_INSTR * 1024, BUF = IN_BYTES + W_INSTR * 1024;
     constexpr int IN_PW = (IN_INSTR + 3) / 4, W_PW = (W_INSTR + 3) / 4;   // wave-instructions per wave and slice
@@ -317,7 +310,7 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
     int in_src[IN_PW], w_src[W_PW];
 #pragma unroll
     for (int i = 0; i < IN_PW; i++) {
-        const int slot = (wv + 4 * i) * 64 + lane, p = slot / PP, q = (slot % PP) ^ glds_swz<PP>(p);
+        const int slot = (wv + 4 * i) * 64 + lane, p = slot / PP, q = (slot % PP) ^ glds_swz(p);
         // LDS pixel p = (halo row * ST + column parity) * PW + column / ST
         const int prow = p / PW, hy = prow / ST, hx = (p % PW) * ST + prow % ST;
         int yy = iy0 + hy, xx = ix0 + hx;
@@ -332,7 +325,7 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
     }
 #pragma unroll
     for (int i = 0; i < W_PW; i++) {
-        const int slot = (wv + 4 * i) * 64 + lane, rw = slot / PP, q = (slot % PP) ^ glds_swz<PP>(rw);
+        const int slot = (wv + 4 * i) * 64 + lane, rw = slot / PP, q = (slot % PP) ^ glds_swz(rw);
         w_src[i] = (int)wt_off(rw / BN, co0 + rw % BN, q * 8, KS * KS, Cout);      // + the slice: c0 / 16 * (KK * Cout * 16) elements
     }
     // `part` / `nparts`: issue the wave's DMA instructions i with i % nparts == part (all of them for nparts = 1) -- the main loop spreads
@@ -387,7 +380,7 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
 #pragma unroll
                 for (int hr = 0; hr < NA; hr++) {
                     const int p = (RPW * wv + hr) * PW + m + sc;
-                    ad[hr] = *reinterpret_cast<const bf16x8 *>(s_in + (p * PP + (qa ^ glds_swz<PP>(p))) * 16);
+                    ad[hr] = *reinterpret_cast<const bf16x8 *>(s_in + (p * PP + (qa ^ glds_swz(p))) * 16);
                 }
             };
             auto load_b = [&](int t, bf16x8 *bd) {           // step t = (phase, tap row r)
@@ -395,7 +388,7 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
 #pragma unroll
                 for (int nb = 0; nb < NB; nb++) {
                     const int rw = (KS * r + sc) * BN + nb * 32 + m;
-                    bd[nb] = *reinterpret_cast<const bf16x8 *>(s_w + (rw * PP + (qa ^ glds_swz<PP>(rw))) * 16);
+                    bd[nb] = *reinterpret_cast<const bf16x8 *>(s_w + (rw * PP + (qa ^ glds_swz(rw))) * 16);
                 }
             };
             load_a(0, a[0]);
@@ -432,7 +425,7 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
 #pragma unroll
                     for (int hr = 0; hr < RPW + KS - 1; hr++) {
                         const int p = (RPW * wv + hr) * PW + m + s;
-                        a[hr] = *reinterpret_cast<const bf16x8 *>(s_in + (p * PP + (qa ^ glds_swz<PP>(p))) * 16);
+                        a[hr] = *reinterpret_cast<const bf16x8 *>(s_in + (p * PP + (qa ^ glds_swz(p))) * 16);
                     }
 #pragma unroll
                     for (int r = 0; r < KS; r++) {
@@ -440,7 +433,7 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
 #pragma unroll
                         for (int nb = 0; nb < NB; nb++) {
                             const int rw = (KS * r + s) * BN + nb * 32 + m;
-                            b[nb] = *reinterpret_cast<const bf16x8 *>(s_w + (rw * PP + (qa ^ glds_swz<PP>(rw))) * 16);
+                            b[nb] = *reinterpret_cast<const bf16x8 *>(s_w + (rw * PP + (qa ^ glds_swz(rw))) * 16);
                         }
                         constexpr int NPARTS = OCTA_DMA_PARTS;
                         const int t = (ks * KS + s) * KS + r;
@@ -471,12 +464,12 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
                     for (int rr = 0; rr < RPW; rr++) {
                         const int hy = (RPW * wv + rr) * ST + r;                       // halo row; halo column = m * ST + s
                         const int p = (hy * ST + (ST == 2 ? (s & 1) : 0)) * PW + m + (ST == 2 ? (s >> 1) : s);
-                        a[rr] = *reinterpret_cast<const bf16x8 *>(s_in + (p * PP + (qa ^ glds_swz<PP>(p))) * 16);
+                        a[rr] = *reinterpret_cast<const bf16x8 *>(s_in + (p * PP + (qa ^ glds_swz(p))) * 16);
                     }
 #pragma unroll
                     for (int nb = 0; nb < NB; nb++) {
                         const int rw = (KS * r + s) * BN + nb * 32 + m;
-                        b[nb] = *reinterpret_cast<const bf16x8 *>(s_w + (rw * PP + (qa ^ glds_swz<PP>(rw))) * 16);
+                        b[nb] = *reinterpret_cast<const bf16x8 *>(s_w + (rw * PP + (qa ^ glds_swz(rw))) * 16);
                     }
 #pragma unroll
                     for (int rr = 0; rr < RPW; rr++)
@@ -486,7 +479,8 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
                 }
     }
     if (!MASKED) { osc = 1; ooy = 0; oox = 0; }   // the scattered store is compiled into the masked variant only (its only user)
-    // epilogue of the plain kernel: tile through LDS, 16-byte coalesced NHWC stores
+    // epilogue: the tile goes through LDS ([pixel][BN channels], 16-byte padded rows) so that consecutive threads write consecutive
+    // 16-byte pieces -- whole 64/128-byte pixel rows -- instead of 2-byte elements 64 bytes apart
     unsigned short *Yo = co0 < CY1 ? Y : Y2;
     const int ys = co0 < CY1 ? CY1 : Cout - CY1, yb = co0 < CY1 ? co0 : co0 - CY1;
     constexpr int OP = BN * 2 + 16;
@@ -625,39 +619,30 @@ conv3x3_nhwc_glds_kernel(const unsigned short *__restrict__ X, const unsigned sh
     }
 }
 
-template <int BN, int KCV, int ST = 1, int KS = 3, int THT = TH>
-int launch_conv_glds(const unsigned short *X, const unsigned short *X2, int C1, const unsigned short *Wt, unsigned short *Y, unsigned short *Y2,
-                     int CY1, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int dil, const unsigned short *zero16, float *part, int tap_mask,
-                     int osc, int ooy, int oox, hipStream_t stream, int pad = 1, const unsigned short *R = nullptr, int reflect = 0, int nslot = 0) {
-    constexpr int IH = (THT - 1) * ST + KS, IW = (TW - 1) * ST + KS, PP = KCV / 8;
+template <int BN, int ST = 1, int KS = 3, int THT = TH>
+int launch_conv_glds(const FwdLaunch &L) {
+    constexpr int IH = (THT - 1) * ST + KS, IW = (TW - 1) * ST + KS;
     constexpr int BUF = ((IH * ST * ((IW + ST - 1) / ST) * PP + 63) / 64 + KS * KS * BN * PP / 64) * 1024;
     constexpr int OUT = THT * TW * (BN * 2 + 16) + 16 + 4 * BN * 2 * 4;      // output tile + the statistics epilogue's [4 waves][BN][2] floats behind it
     const size_t lds = 2 * BUF > OUT ? 2 * BUF : OUT;
-    const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + THT - 1) / THT;
-    auto kern = conv3x3_nhwc_glds_kernel<BN, KCV, false, false, ST, KS, THT>;
+    const int tiles_x = (L.Wo + TW - 1) / TW, tiles_y = (L.Ho + THT - 1) / THT;
+    auto kern = conv3x3_nhwc_glds_kernel<BN, false, false, ST, KS, THT>;
     if constexpr (KS == 3) {
-        if (part) kern = tap_mask != 0x1ff || osc != 1 ? conv3x3_nhwc_glds_kernel<BN, KCV, true, true, ST, 3, THT> : conv3x3_nhwc_glds_kernel<BN, KCV, true, false, ST, 3, THT>;
-        else if (tap_mask != 0x1ff || osc != 1) kern = conv3x3_nhwc_glds_kernel<BN, KCV, false, true, ST, 3, THT>;
+        const bool masked = L.tap_mask != 0x1ff || L.osc != 1;      // the masked form is also the one with the scattered store
+        if constexpr (THT == TH) {
+            if (masked) kern = L.part ? conv3x3_nhwc_glds_kernel<BN, true, true, ST, 3, THT> : conv3x3_nhwc_glds_kernel<BN, false, true, ST, 3, THT>;
+        } else if (masked) {                                        // the 16-row tile exists for all taps and a plain store only
+            octa::set_error("conv: the 16-row tile was asked for with a tap mask or an output scatter");
+            return -2;
+        }
+        if (!masked && L.part) kern = conv3x3_nhwc_glds_kernel<BN, true, false, ST, 3, THT>;
     }
     OCTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(Cout / BN), (unsigned)N);
-    hipLaunchKernelGGL(kern, grid, dim3(CONV_THREADS), lds, stream, X, X2, C1, Wt, Y, Y2, CY1, H, W, Cin, Ho, Wo, Cout, dil, tiles_x, zero16, part, tap_mask, osc, ooy, oox, pad, R, reflect, nslot);
+    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(L.Cout / BN), (unsigned)L.N);
+    hipLaunchKernelGGL(kern, grid, dim3(CONV_THREADS), lds, L.stream, L.X, L.X2, L.C1, L.Wt, L.Y, L.Y2, L.CY1, L.H, L.W, L.Cin, L.Ho, L.Wo, L.Cout, L.dil,
+                       tiles_x, L.zero16, L.part, L.tap_mask, L.osc, L.ooy, L.oox, L.pad, L.R, L.reflect, L.nslot);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
-}
-
-template <int BN, int ST>
-int launch_conv(const unsigned short *X, const unsigned short *X2, int C1, const unsigned short *Wt, unsigned short *Y, unsigned short *Y2,
-                int CY1, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int dil, int tap_mask, int osc, int ooy, int oox,
-                const float *sc1, const float *sh1, const float *sc2, const float *sh2, float slope, float *part, hipStream_t stream) {
-    if (sc1 || sc2 || part || osc != 1)
-        return launch_conv_impl<BN, ST, true, true>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, dil, tap_mask, osc, ooy, oox, sc1, sh1, sc2,
-                                                    sh2, slope, part, stream);
-    if (tap_mask != 0x1ff)
-        return launch_conv_impl<BN, ST, false, true>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, dil, tap_mask, 1, 0, 0, nullptr, nullptr,
-                                                     nullptr, nullptr, 0.f, nullptr, stream);
-    return launch_conv_impl<BN, ST, false, false>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, dil, tap_mask, 1, 0, 0, nullptr, nullptr,
-                                                  nullptr, nullptr, 0.f, nullptr, stream);
 }
 
 // ---- stride-2 "up" convolution with the four output parities fused (round 5) ------------------------------------------------------
@@ -674,7 +659,7 @@ template <int BN>
 __global__ void __launch_bounds__(CONV_THREADS, 2)
 conv3x3_s2t_kernel(const unsigned short *__restrict__ X, const unsigned short *__restrict__ Wt, unsigned short *__restrict__ Y, int H, int W, int Cin,
                    int Cout, int tiles_x, const unsigned short *__restrict__ zero16, int tap_mask, const unsigned short *__restrict__ R) {
-    constexpr int KCV = 16, PP = 2, NB = BN / 32, RPW = 2;
+    constexpr int NB = BN / 32, RPW = 2;
     constexpr int IH = TH + 1, IW = TW + 1, LPIX = IH * IW;
     constexpr int IN_INSTR = (LPIX * PP + 63) / 64, W_INSTR = 9 * BN * PP / 64;
     constexpr int IN_BYTES = IN_INSTR * 1024, BUF = IN_BYTES + W_INSTR * 1024;
@@ -687,14 +672,14 @@ conv3x3_s2t_kernel(const unsigned short *__restrict__ X, const unsigned short *_
     int in_src[IN_PW], w_src[W_PW];
 #pragma unroll
     for (int i = 0; i < IN_PW; i++) {
-        const int slot = (wv + 4 * i) * 64 + lane, p = slot / PP, q = (slot % PP) ^ glds_swz<PP>(p);
+        const int slot = (wv + 4 * i) * 64 + lane, p = slot / PP, q = (slot % PP) ^ glds_swz(p);
         const int yy = ty0 + p / IW, xx = tx0 + p % IW;
         const bool ok = p < LPIX && yy < H && xx < W;
         in_src[i] = ok ? ((yy * W + xx) << 2) | q : -1;
     }
 #pragma unroll
     for (int i = 0; i < W_PW; i++) {
-        const int slot = (wv + 4 * i) * 64 + lane, rw = slot / PP, q = (slot % PP) ^ glds_swz<PP>(rw);
+        const int slot = (wv + 4 * i) * 64 + lane, rw = slot / PP, q = (slot % PP) ^ glds_swz(rw);
         w_src[i] = (int)wt_off(rw / BN, co0 + rw % BN, q * 8, 9, Cout);
     }
     const unsigned short *img = X + (size_t)n * H * W * Cin;
@@ -735,7 +720,7 @@ conv3x3_s2t_kernel(const unsigned short *__restrict__ X, const unsigned short *_
 #pragma unroll
             for (int ox = 0; ox < 2; ox++) {
                 const int p = (RPW * wv + hr) * IW + m + ox;
-                a[hr][ox] = *reinterpret_cast<const bf16x8 *>(s_in + (p * PP + (kg ^ glds_swz<PP>(p))) * 16);
+                a[hr][ox] = *reinterpret_cast<const bf16x8 *>(s_in + (p * PP + (kg ^ glds_swz(p))) * 16);
             }
 #pragma unroll
         for (int kr = 0; kr < 3; kr++)
@@ -746,7 +731,7 @@ conv3x3_s2t_kernel(const unsigned short *__restrict__ X, const unsigned short *_
 #pragma unroll
                 for (int nb = 0; nb < NB; nb++) {
                     const int rw = (3 * kr + ks) * BN + nb * 32 + m;
-                    const bf16x8 b = *reinterpret_cast<const bf16x8 *>(s_w + (rw * PP + (kg ^ glds_swz<PP>(rw))) * 16);
+                    const bf16x8 b = *reinterpret_cast<const bf16x8 *>(s_w + (rw * PP + (kg ^ glds_swz(rw))) * 16);
 #pragma unroll
                     for (int rr = 0; rr < RPW; rr++)
                         acc[cls][rr][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rr + oy][ox], b, acc[cls][rr][nb], 0, 0, 0);
@@ -803,19 +788,54 @@ conv3x3_s2t_kernel(const unsigned short *__restrict__ X, const unsigned short *_
 }
 
 template <int BN>
-int launch_conv_s2t(const unsigned short *X, const unsigned short *Wt, unsigned short *Y, int N, int H, int W, int Cin, int Cout, const unsigned short *zero16,
-                    int tap_mask, const unsigned short *R, hipStream_t stream) {
-    constexpr int PP = 2;
+int launch_conv_s2t(const FwdLaunch &L) {
     constexpr int BUF = (((TH + 1) * (TW + 1) * PP + 63) / 64 + 9 * BN * PP / 64) * 1024;
     constexpr int OUT = 8 * (2 * TW) * (BN * 2 + 16);
     const size_t lds = 2 * BUF > OUT ? 2 * BUF : OUT;
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
+    const int tiles_x = (L.W + TW - 1) / TW, tiles_y = (L.H + TH - 1) / TH;
     auto kern = conv3x3_s2t_kernel<BN>;
     OCTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(Cout / BN), (unsigned)N);
-    hipLaunchKernelGGL(kern, grid, dim3(CONV_THREADS), lds, stream, X, Wt, Y, H, W, Cin, Cout, tiles_x, zero16, tap_mask, R);
+    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(L.Cout / BN), (unsigned)L.N);
+    hipLaunchKernelGGL(kern, grid, dim3(CONV_THREADS), lds, L.stream, L.X, L.Wt, L.Y, L.H, L.W, L.Cin, L.Cout, tiles_x, L.zero16, L.tap_mask, L.R);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+// ---- the argument checks the entry points share. Each sets the error under the entry point's name `fn` and returns true when it refuses
+// the call (return code -2 everywhere) ------------------------------------------------------------------------------------------------------
+constexpr int MAX_IMAGES = 65535;      // N is gridDim.z of the forward kernels
+
+bool null_pointer(const char *fn, const void *ctx, const void *a, const void *b, const void *c) {
+    if (ctx && a && b && c) return false;
+    octa::set_error("%s: null pointer", fn);
+    return true;
+}
+
+// N, H, W positive, and whatever else (`other`) the entry point counts as a bad shape
+bool bad_shape(const char *fn, int N, int H, int W, bool other = false) {
+    if (N > 0 && H > 0 && W > 0 && !other) return false;
+    octa::set_error("%s: bad shape", fn);
+    return true;
+}
+
+bool bad_channels(const char *fn, int Cin, int Cout) {
+    if (Cin % 32 == 0 && Cout % 32 == 0 && Cin > 0 && Cout > 0) return false;
+    octa::set_error("%s: Cin and Cout must be multiples of 32 (got %d, %d)", fn, Cin, Cout);
+    return true;
+}
+
+// explicit padding of a stride-1 3x3 layer (octa_conv3x3_nhwc_fwd_pad and its weight gradient): pad 0..2 with at least one output pixel;
+// reflect only with pad = 1 and something to mirror
+bool bad_pad(const char *fn, int H, int W, int pad, int reflect) {
+    if (pad < 0 || pad > 2 || H + 2 * pad < 3 || W + 2 * pad < 3) { octa::set_error("%s: bad shape", fn); return true; }
+    if (reflect && (pad != 1 || H < 2 || W < 2)) { octa::set_error("%s: reflection needs pad = 1 and an image of at least 2 x 2", fn); return true; }
+    return false;
+}
+
+bool bad_out_mode(const char *fn, int out_mode) {
+    if (out_mode >= OCTA_WGRAD_TAP_MAJOR && out_mode <= OCTA_WGRAD_PARAM_SET) return false;
+    octa::set_error("%s: out_mode %d is none of OCTA_WGRAD_*", fn, out_mode);
+    return true;
 }
 
 }  // namespace
@@ -836,14 +856,12 @@ extern "C" int octa_conv3x3_nhwc_fwd(octa_ctx *ctx, const octa_conv3x3_args *a, 
     const float slope = a->slope;
     float *d_stat_partials = a->d_stat_partials;
     double *d_stat_slots = a->d_stat_slots;
-    if (!ctx || !d_x || !d_w || !d_y) { octa::set_error("octa_conv3x3_nhwc_fwd: null pointer"); return -2; }
-    if (N <= 0 || H <= 0 || W <= 0) { octa::set_error("octa_conv3x3_nhwc_fwd: bad shape"); return -2; }
-    if (Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) { octa::set_error("octa_conv3x3_nhwc_fwd: Cin and Cout must be multiples of 32 (got %d, %d)", Cin, Cout); return -2; }
+    if (null_pointer(__func__, ctx, d_x, d_w, d_y) || bad_shape(__func__, N, H, W) || bad_channels(__func__, Cin, Cout)) return -2;
     if ((stride != 1 && stride != 2) || (in_dilation != 1 && in_dilation != 2) || (stride == 2 && in_dilation == 2)) {
         octa::set_error("octa_conv3x3_nhwc_fwd: stride %d / input dilation %d not supported", stride, in_dilation);
         return -2;
     }
-    if (N > 65535) { octa::set_error("octa_conv3x3_nhwc_fwd: N > 65535"); return -2; }
+    if (N > MAX_IMAGES) { octa::set_error("octa_conv3x3_nhwc_fwd: N > 65535"); return -2; }
     if (!d_x2) C1 = Cin;
     if (!d_y2) CY1 = Cout;
     tap_mask &= 0x1ff;
@@ -863,34 +881,30 @@ extern "C" int octa_conv3x3_nhwc_fwd(octa_ctx *ctx, const octa_conv3x3_args *a, 
     }
     if ((d_scale1 == nullptr) != (d_shift1 == nullptr) || (d_scale2 == nullptr) != (d_shift2 == nullptr)) { octa::set_error("octa_conv3x3_nhwc_fwd: scale and shift come in pairs"); return -2; }
     if (C1 <= 0 || C1 > Cin || C1 % 32 || CY1 <= 0 || CY1 > Cout || CY1 % 32) { octa::set_error("octa_conv3x3_nhwc_fwd: channel splits must be multiples of 32 inside the channel range"); return -2; }
-    hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    const int Hv = H * in_dilation, Wv = W * in_dilation;
-    const int Ho = (Hv + 2 - 3) / stride + 1, Wo = (Wv + 2 - 3) / stride + 1;
-    const unsigned short *X = static_cast<const unsigned short *>(d_x), *X2 = static_cast<const unsigned short *>(d_x2);
-    const unsigned short *Wt = static_cast<const unsigned short *>(d_w);
-    unsigned short *Y = static_cast<unsigned short *>(d_y), *Y2 = static_cast<unsigned short *>(d_y2);
+    FwdLaunch L;
+    L.X = static_cast<const unsigned short *>(d_x), L.X2 = static_cast<const unsigned short *>(d_x2), L.Wt = static_cast<const unsigned short *>(d_w);
+    L.Y = static_cast<unsigned short *>(d_y), L.Y2 = static_cast<unsigned short *>(d_y2);
+    L.C1 = C1, L.CY1 = CY1, L.N = N, L.H = H, L.W = W, L.Cin = Cin, L.Cout = Cout, L.dil = in_dilation;
+    L.Ho = (H * in_dilation + 2 - 3) / stride + 1, L.Wo = (W * in_dilation + 2 - 3) / stride + 1;
+    L.tap_mask = tap_mask, L.osc = out_scale, L.ooy = out_off_y, L.oox = out_off_x;
+    L.sc1 = d_scale1, L.sh1 = d_shift1, L.sc2 = d_scale2, L.sh2 = d_shift2, L.slope = slope;
+    L.part = d_stat_partials, L.nslot = nslot, L.R = Rz, L.stream = (hipStream_t)stream_;
     const bool wide = (Cout % 64 == 0) && (CY1 % 64 == 0);   // a 64-channel block must not straddle the output split
-    // without normalise-on-load operands: the DMA-staged kernels, 16-channel slices (only they have the residual and the slot epilogue,
-    // both refused above beside scale / shift); with them: the register-staged kernels below
-    if (!d_scale1 && !d_scale2) {
-        const unsigned short *z = zero_page(ctx);
-        if (!z) return -1;
-        if (stride == 2)
-            return wide ? launch_conv_glds<64, 16, 2>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, 1, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot)
-                        : launch_conv_glds<32, 16, 2>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, 1, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot);
-        // 16-row tiles (a wave owns four tile rows: 6 operand reads per 8 MFMAs instead of 4 per 4, 72 MFMAs per barrier) from
-        // 200 output rows up: 8-14 % faster on the 304^2 / 608^2 layers (256->128 at 304^2: 1.0 PFLOP/s), no gain at 152^2
-        // (half as many workgroups: tail effects) and on the HBM-bound 1216^2 layers.
-        if (wide && tap_mask == 0x1ff && out_scale == 1 && Ho >= 200)
-            return launch_conv_glds<64, 16, 1, 3, 16>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, 1, 0, 0, stream, 1, Rz, 0, nslot);
-        return wide ? launch_conv_glds<64, 16>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot)
-                    : launch_conv_glds<32, 16>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, z, d_stat_partials, tap_mask, out_scale, out_off_y, out_off_x, stream, 1, Rz, 0, nslot);
+    // with normalise-on-load operands: the register-staged kernel; without them: the DMA-staged kernels, 16-channel slices (only
+    // they have the residual and the slot epilogue, both refused above beside scale / shift)
+    if (d_scale1 || d_scale2) {
+        if (stride == 1) return wide ? launch_conv<64, 1>(L) : launch_conv<32, 1>(L);
+        return wide ? launch_conv<64, 2>(L) : launch_conv<32, 2>(L);
     }
-    if (stride == 1) return wide ? launch_conv<64, 1>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, tap_mask, out_scale, out_off_y, out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, stream)
-                                 : launch_conv<32, 1>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, tap_mask, out_scale, out_off_y, out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, stream);
-    return wide ? launch_conv<64, 2>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, tap_mask, out_scale, out_off_y, out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, stream)
-                : launch_conv<32, 2>(X, X2, C1, Wt, Y, Y2, CY1, N, H, W, Cin, Ho, Wo, Cout, in_dilation, tap_mask, out_scale, out_off_y, out_off_x, d_scale1, d_shift1, d_scale2, d_shift2, slope, d_stat_partials, stream);
+    L.zero16 = zero_page(ctx);
+    if (!L.zero16) return -1;
+    if (stride == 2) return wide ? launch_conv_glds<64, 2>(L) : launch_conv_glds<32, 2>(L);
+    // 16-row tiles (a wave owns four tile rows: 6 operand reads per 8 MFMAs instead of 4 per 4, 72 MFMAs per barrier) from
+    // 200 output rows up: 8-14 % faster on the 304^2 / 608^2 layers (256->128 at 304^2: 1.0 PFLOP/s), no gain at 152^2
+    // (half as many workgroups: tail effects) and on the HBM-bound 1216^2 layers.
+    if (wide && tap_mask == 0x1ff && out_scale == 1 && L.Ho >= 200) return launch_conv_glds<64, 1, 3, 16>(L);
+    return wide ? launch_conv_glds<64>(L) : launch_conv_glds<32>(L);
 }
 
 // d_x [N][H][W][Cin] bf16 (the SMALL image), d_w [9][Cout][Cin] bf16 packed as for the zero-insertion form (octa_conv3x3_nhwc_fwd with
@@ -898,38 +912,34 @@ extern "C" int octa_conv3x3_nhwc_fwd(octa_ctx *ctx, const octa_conv3x3_args *a, 
 // stride-2 3x3 layer; 0b000011011: the 2x2 stride-2 transposed convolution); d_residual (shape of d_y, may be NULL) is added as octa_conv3x3_nhwc_fwd adds it.
 extern "C" int octa_conv3x3_s2t_nhwc(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int tap_mask,
                                      const void *d_residual, void *stream_) {
-    if (!ctx || !d_x || !d_w || !d_y) { octa::set_error("octa_conv3x3_s2t_nhwc: null pointer"); return -2; }
-    if (N <= 0 || N > 65535 || H <= 0 || W <= 0) { octa::set_error("octa_conv3x3_s2t_nhwc: bad shape"); return -2; }
-    if (Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) { octa::set_error("octa_conv3x3_s2t_nhwc: Cin and Cout must be multiples of 32 (got %d, %d)", Cin, Cout); return -2; }
+    if (null_pointer(__func__, ctx, d_x, d_w, d_y) || bad_shape(__func__, N, H, W, N > MAX_IMAGES) || bad_channels(__func__, Cin, Cout)) return -2;
     tap_mask &= 0x1ff;
     if (tap_mask == 0 || d_residual == d_y) { octa::set_error("octa_conv3x3_s2t_nhwc: empty tap mask or residual aliasing the output"); return -2; }
-    hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    const unsigned short *z = zero_page(ctx);
-    if (!z) return -1;
-    const unsigned short *X = static_cast<const unsigned short *>(d_x), *Wt = static_cast<const unsigned short *>(d_w), *R = static_cast<const unsigned short *>(d_residual);
-    unsigned short *Y = static_cast<unsigned short *>(d_y);
+    FwdLaunch L;
+    L.zero16 = zero_page(ctx);
+    if (!L.zero16) return -1;
+    L.X = static_cast<const unsigned short *>(d_x), L.Wt = static_cast<const unsigned short *>(d_w), L.Y = static_cast<unsigned short *>(d_y);
+    L.R = static_cast<const unsigned short *>(d_residual);
+    L.N = N, L.H = H, L.W = W, L.Cin = Cin, L.Cout = Cout, L.tap_mask = tap_mask, L.stream = (hipStream_t)stream_;
     // 32 output channels per workgroup everywhere: 128 accumulator registers, two workgroups per CU. The 64-channel form (256 accumulator
     // registers in AGPRs, one workgroup of four waves per CU) measured slower on every layer (data gradients 159 / 238 / 260 us against
     // 123 / 169 / 262, transposed convolutions 90 / 118 / 128 against 74 / 96 / 129; zero-insertion form: 180 / 212 / 296 and 112 / 131 / 245).
-    return launch_conv_s2t<32>(X, Wt, Y, N, H, W, Cin, Cout, z, tap_mask, R, stream);
+    return launch_conv_s2t<32>(L);
 }
 
 extern "C" int octa_conv4x4_nhwc_fwd(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int pad,
                                      void *stream_) {
-    if (!ctx || !d_x || !d_w || !d_y) { octa::set_error("octa_conv4x4_nhwc_fwd: null pointer"); return -2; }
-    if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || pad < 0 || pad > 3 || H + 2 * pad < 4 || W + 2 * pad < 4) { octa::set_error("octa_conv4x4_nhwc_fwd: bad shape"); return -2; }
-    if (Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) { octa::set_error("octa_conv4x4_nhwc_fwd: Cin and Cout must be multiples of 32 (got %d, %d)", Cin, Cout); return -2; }
-    hipStream_t stream = (hipStream_t)stream_;
+    if (null_pointer(__func__, ctx, d_x, d_w, d_y)) return -2;
+    if (bad_shape(__func__, N, H, W, N > MAX_IMAGES || pad < 0 || pad > 3 || H + 2 * pad < 4 || W + 2 * pad < 4) || bad_channels(__func__, Cin, Cout)) return -2;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    const unsigned short *z = zero_page(ctx);
-    if (!z) return -1;
-    const int Ho = H + 2 * pad - 3, Wo = W + 2 * pad - 3;
-    const unsigned short *X = static_cast<const unsigned short *>(d_x), *Wt = static_cast<const unsigned short *>(d_w);
-    unsigned short *Y = static_cast<unsigned short *>(d_y);
-    if (Cout % 64 == 0)
-        return launch_conv_glds<64, 16, 1, 4>(X, nullptr, Cin, Wt, Y, nullptr, Cout, N, H, W, Cin, Ho, Wo, Cout, 1, z, nullptr, 0xffff, 1, 0, 0, stream, pad);
-    return launch_conv_glds<32, 16, 1, 4>(X, nullptr, Cin, Wt, Y, nullptr, Cout, N, H, W, Cin, Ho, Wo, Cout, 1, z, nullptr, 0xffff, 1, 0, 0, stream, pad);
+    FwdLaunch L;
+    L.zero16 = zero_page(ctx);
+    if (!L.zero16) return -1;
+    L.X = static_cast<const unsigned short *>(d_x), L.Wt = static_cast<const unsigned short *>(d_w), L.Y = static_cast<unsigned short *>(d_y);
+    L.C1 = Cin, L.CY1 = Cout, L.N = N, L.H = H, L.W = W, L.Cin = Cin, L.Cout = Cout, L.Ho = H + 2 * pad - 3, L.Wo = W + 2 * pad - 3;
+    L.tap_mask = 0xffff, L.pad = pad, L.stream = (hipStream_t)stream_;
+    return Cout % 64 == 0 ? launch_conv_glds<64, 1, 4>(L) : launch_conv_glds<32, 1, 4>(L);
 }
 
 // 3 x 3 convolution, stride 1, with an explicit padding: pad = 0 (valid), 1 (same) or 2 (full: what the data gradient of a valid
@@ -940,25 +950,20 @@ extern "C" int octa_conv4x4_nhwc_fwd(octa_ctx *ctx, const void *d_x, const void 
 // them per pass, and each paid a statistics launch over a tensor that had just been written.
 extern "C" int octa_conv3x3_nhwc_fwd_pad(octa_ctx *ctx, const void *d_x, const void *d_w, void *d_y, int N, int H, int W, int Cin, int Cout, int pad,
                                          int reflect, double *d_stat_slots, int nslot, void *stream_) {
-    if (!ctx || !d_x || !d_w || !d_y) { octa::set_error("octa_conv3x3_nhwc_fwd_pad: null pointer"); return -2; }
+    if (null_pointer(__func__, ctx, d_x, d_w, d_y)) return -2;
     if (d_stat_slots && (nslot <= 0 || nslot > 1024)) { octa::set_error("octa_conv3x3_nhwc_fwd_pad: statistics slots need 1..1024 slots"); return -2; }
     if (!d_stat_slots) nslot = 0;
-    float *part = reinterpret_cast<float *>(d_stat_slots);      // one kernel argument: read as double slots when nslot > 0
-    if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || pad < 0 || pad > 2 || H + 2 * pad < 3 || W + 2 * pad < 3) { octa::set_error("octa_conv3x3_nhwc_fwd_pad: bad shape"); return -2; }
-    if (reflect && (pad != 1 || H < 2 || W < 2)) { octa::set_error("octa_conv3x3_nhwc_fwd_pad: reflection needs pad = 1 and an image of at least 2 x 2"); return -2; }
-    if (Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) { octa::set_error("octa_conv3x3_nhwc_fwd_pad: Cin and Cout must be multiples of 32 (got %d, %d)", Cin, Cout); return -2; }
-    hipStream_t stream = (hipStream_t)stream_;
+    if (bad_shape(__func__, N, H, W, N > MAX_IMAGES) || bad_pad(__func__, H, W, pad, reflect) || bad_channels(__func__, Cin, Cout)) return -2;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    const unsigned short *z = zero_page(ctx);
-    if (!z) return -1;
-    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
-    const unsigned short *X = static_cast<const unsigned short *>(d_x), *Wt = static_cast<const unsigned short *>(d_w);
-    unsigned short *Y = static_cast<unsigned short *>(d_y);
-    if (Cout % 64 == 0) {
-        if (Ho >= 200) return launch_conv_glds<64, 16, 1, 3, 16>(X, nullptr, Cin, Wt, Y, nullptr, Cout, N, H, W, Cin, Ho, Wo, Cout, 1, z, part, 0x1ff, 1, 0, 0, stream, pad, nullptr, reflect, nslot);
-        return launch_conv_glds<64, 16>(X, nullptr, Cin, Wt, Y, nullptr, Cout, N, H, W, Cin, Ho, Wo, Cout, 1, z, part, 0x1ff, 1, 0, 0, stream, pad, nullptr, reflect, nslot);
-    }
-    return launch_conv_glds<32, 16>(X, nullptr, Cin, Wt, Y, nullptr, Cout, N, H, W, Cin, Ho, Wo, Cout, 1, z, part, 0x1ff, 1, 0, 0, stream, pad, nullptr, reflect, nslot);
+    FwdLaunch L;
+    L.zero16 = zero_page(ctx);
+    if (!L.zero16) return -1;
+    L.X = static_cast<const unsigned short *>(d_x), L.Wt = static_cast<const unsigned short *>(d_w), L.Y = static_cast<unsigned short *>(d_y);
+    L.C1 = Cin, L.CY1 = Cout, L.N = N, L.H = H, L.W = W, L.Cin = Cin, L.Cout = Cout, L.Ho = H + 2 * pad - 2, L.Wo = W + 2 * pad - 2;
+    L.tap_mask = 0x1ff, L.pad = pad, L.reflect = reflect, L.stream = (hipStream_t)stream_;
+    L.part = reinterpret_cast<float *>(d_stat_slots), L.nslot = nslot;      // one kernel argument: read as double slots when nslot > 0
+    if (Cout % 64 == 0) return L.Ho >= 200 ? launch_conv_glds<64, 1, 3, 16>(L) : launch_conv_glds<64>(L);
+    return launch_conv_glds<32>(L);
 }
 
 // ---- weight gradient (stride 1) ----------------------------------------------------------------------------------
@@ -987,7 +992,7 @@ constexpr int HALO_W = 40;             // halo row pitch in pixels (34 used; 80 
 // is compiled for two resident workgroups -- twice the loads in flight; the larger tiles need the whole register file.
 template <int COB, int CIB, int ST, int KS = 3> constexpr int wgrad_wgs_per_cu() { return COB == 32 && CIB == 32 && ST == 1 && KS == 3 ? 2 : 1; }
 
-template <int COB, int CIB, bool MASKED, int ST, bool XFORM, int KS>
+template <int COB, int CIB, bool MASKED, int ST, int KS>
 __global__ void __launch_bounds__(CONV_THREADS, (wgrad_wgs_per_cu<COB, CIB, ST, KS>()))
 conv3x3_nhwc_wgrad_kernel(const unsigned short *__restrict__ X, const unsigned short *__restrict__ X2, int C1,
                           const unsigned short *__restrict__ dY, float *__restrict__ dW,
@@ -999,7 +1004,8 @@ conv3x3_nhwc_wgrad_kernel(const unsigned short *__restrict__ X, const unsigned s
     constexpr int ROWS_PER_WAVE = WTH / KSPLIT;
     constexpr int SLOTS = ROWS_PER_WAVE * (TW / 16);   // MFMA groups of the compute loop = places to tuck LDS stores
     constexpr int XROWS = ST == 1 ? WTH + KS - 1 : 2 * WTH + 1, XCOLS = ST == 1 ? TW + KS - 1 : 2 * TW + 1;   // KS x KS taps (4: the PatchGAN, stride 1 only)
-    static_assert(KS == 3 || (KS == 4 && ST == 1 && !MASKED && !XFORM), "4x4 taps: plain stride-1 variant only");
+    static_assert(KS == 3 || (KS == 4 && ST == 1 && !MASKED), "4x4 taps: plain stride-1 variant only");
+    constexpr bool XFORM = KS == 3;              // normalise-on-load is compiled into the 3x3 form only: the 4x4 layers have no use for it
     constexpr int XRP = ST == 1 ? HALO_W * 2 : 2 * HALO_W * 2;      // bytes per halo row (two column-parity planes for ST = 2)
     constexpr int WG_XROW = wg_pad_pitch(XROWS * XRP);               // bytes per channel row of the transposed X tile
     constexpr int DYPIX = WTH * TW, XPIX = XROWS * XCOLS;
@@ -1013,7 +1019,7 @@ conv3x3_nhwc_wgrad_kernel(const unsigned short *__restrict__ X, const unsigned s
     const int xcs = ci0 < C1 ? C1 : Cin - C1, xcb = ci0 < C1 ? ci0 : ci0 - C1;
     // normalise-on-load of the layer input (see the forward kernel): per image and channel scale / shift
     const float *scp = ci0 < C1 ? sc1 : sc2, *shp = ci0 < C1 ? sh1 : sh2;
-    const bool xform = XFORM && scp != nullptr;   // compiled into the XFORM variant only (measured slower in the U-Net step)
+    const bool xform = XFORM && scp != nullptr;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int pair = wv % PAIRS, kpart = wv / PAIRS;
     const int cob = (pair % (COB / 32)) * 32, cib = (pair / (COB / 32)) * 32;
@@ -1482,9 +1488,23 @@ wgrad_tr_acc_kernel(const float *__restrict__ ws, float *__restrict__ grad, int 
     if (gridDim.z > 1) atomicAdd(out, v); else if (accumulate) *out += v; else *out = v;
 }
 
+// One weight-gradient launch, filled by the entry point after its checks (as FwdLaunch)
+struct WgradLaunch {
+    const unsigned short *X = nullptr, *X2 = nullptr, *dY = nullptr;     // X2: the second input of a virtual concatenation (channels C1 .. Cin)
+    float *dW = nullptr;                             // layout by out_mode (OCTA_WGRAD_*)
+    int C1 = 0, N = 0, H = 0, W = 0, Cin = 0, Cout = 0, tap_mask = 0x1ff, pad = 1, reflect = 0, out_mode = OCTA_WGRAD_TAP_MAJOR;
+    const float *sc1 = nullptr, *sh1 = nullptr, *sc2 = nullptr, *sh2 = nullptr;   // normalise-on-load (register-staged kernel only)
+    float slope = 0.f;
+    const unsigned short *zero16 = nullptr;
+    hipStream_t stream = nullptr;
+};
+
 template <int COB, int CIB, int ST = 1>
-int launch_wgrad_tr(octa_ctx *ctx, const unsigned short *X, const unsigned short *X2, int C1, const unsigned short *dY, float *dW, int N, int H, int W, int Cin,
-                    int Cout, int num_cus, int tap_mask, const unsigned short *zero16, hipStream_t stream, int pad = 1, int reflect = 0, float *acc = nullptr, int accumulate = 1) {
+int launch_wgrad_tr(octa_ctx *ctx, const WgradLaunch &L) {
+    const int N = L.N, H = L.H, W = L.W, Cin = L.Cin, Cout = L.Cout, pad = L.pad;
+    float *const dW = L.dW, *const acc = L.out_mode ? L.dW : nullptr;      // acc: the parameter-layout buffer wgrad_tr_acc_kernel adds to / overwrites
+    const int accumulate = L.out_mode == OCTA_WGRAD_PARAM_ADD;
+    hipStream_t stream = L.stream;
     // stride 1: 64 x 64 blocks: the 8-row double buffer fits one CU (152 KB); 32 x 32: two workgroups of 76 KB; the mixed blocks keep 4 rows
     // and two workgroups. Stride 2 (a 9 x 66-pixel halo per 4 output rows): 4 rows, one workgroup per CU
     constexpr int TH_ = (ST == 1 && COB == CIB) ? 8 : 4;
@@ -1496,7 +1516,7 @@ int launch_wgrad_tr(octa_ctx *ctx, const unsigned short *X, const unsigned short
     const int Ho = ST == 1 ? H + 2 * pad - 2 : H / ST, Wo = ST == 1 ? W + 2 * pad - 2 : W / ST;
     const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + TH_ - 1) / TH_;
     const int blocks = (Cout / COB) * (Cin / CIB);
-    int per_block = (num_cus * (COB == 32 && CIB == 32 && ST == 1 ? 2 : 1) + blocks - 1) / blocks;
+    int per_block = (ctx->num_cus * (COB == 32 && CIB == 32 && ST == 1 ? 2 : 1) + blocks - 1) / blocks;
     const int n_tiles = tiles_x * tiles_y * N;
     if (per_block > n_tiles) per_block = n_tiles;
     if (per_block < 1) per_block = 1;
@@ -1513,12 +1533,12 @@ int launch_wgrad_tr(octa_ctx *ctx, const unsigned short *X, const unsigned short
         OCTA_HIP_CHECK(hipMemsetAsync(dW, 0, sizeof(float) * 9 * (size_t)Cout * Cin, stream));
     }
     auto kern = conv3x3_nhwc_wgrad_tr_kernel<COB, CIB, TH_, ST, false>;
-    if (tap_mask != 0x1ff) kern = conv3x3_nhwc_wgrad_tr_kernel<COB, CIB, TH_, ST, true>;
-    if constexpr (ST == 2) { if (tap_mask == 0x1b0) kern = conv3x3_nhwc_wgrad_tr_kernel<COB, CIB, TH_, 2, true, false, 0x1b0>; }      // ConvTranspose2d(k = s = 2)
-    if constexpr (ST == 1) { if (reflect) kern = conv3x3_nhwc_wgrad_tr_kernel<COB, CIB, TH_, 1, false, true>; }   // (the mirrored form is never masked: octa_conv3x3_nhwc_wgrad_pad)
+    if (L.tap_mask != 0x1ff) kern = conv3x3_nhwc_wgrad_tr_kernel<COB, CIB, TH_, ST, true>;
+    if constexpr (ST == 2) { if (L.tap_mask == 0x1b0) kern = conv3x3_nhwc_wgrad_tr_kernel<COB, CIB, TH_, 2, true, false, 0x1b0>; }      // ConvTranspose2d(k = s = 2)
+    if constexpr (ST == 1) { if (L.reflect) kern = conv3x3_nhwc_wgrad_tr_kernel<COB, CIB, TH_, 1, false, true>; }   // (the mirrored form is never masked: octa_conv3x3_nhwc_wgrad_pad)
     OCTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)per_block, (unsigned)blocks), dim3(CONV_THREADS), lds, stream, X, X2, C1, dY, dW, N, H, W, Ho, Wo, Cin, Cout,
-                       tiles_x, tiles_y, tap_mask, zero16, ws, pad);
+    hipLaunchKernelGGL(kern, dim3((unsigned)per_block, (unsigned)blocks), dim3(CONV_THREADS), lds, stream, L.X, L.X2, L.C1, L.dY, dW, N, H, W, Ho, Wo, Cin, Cout,
+                       tiles_x, tiles_y, L.tap_mask, L.zero16, ws, pad);
     OCTA_HIP_CHECK(hipGetLastError());
     if (acc) {
         const int slices = per_block > 64 ? (per_block / 32 < 16 ? per_block / 32 : 16) : 1;
@@ -1533,35 +1553,25 @@ int launch_wgrad_tr(octa_ctx *ctx, const unsigned short *X, const unsigned short
     return 0;
 }
 
-template <int COB, int CIB, bool MASKED, int ST, int KS = 3>
-int launch_wgrad_impl(const unsigned short *X, const unsigned short *X2, int C1, const unsigned short *dY, float *dW, int N, int H, int W, int Cin,
-                 int Cout, int num_cus, int tap_mask, const float *sc1, const float *sh1, const float *sc2, const float *sh2, float slope,
-                 const unsigned short *zero16, hipStream_t stream) {
+template <int COB, int CIB, int ST = 1, int KS = 3>
+int launch_wgrad(octa_ctx *ctx, const WgradLaunch &L) {
     constexpr int XROWS = ST == 1 ? WTH + KS - 1 : 2 * WTH + 1;
     constexpr int WG_XROW = wg_pad_pitch(XROWS * (ST == 1 ? HALO_W * 2 : 2 * HALO_W * 2));
     const size_t lds = 2 * ((size_t)COB * WG_ROWP + (size_t)CIB * WG_XROW);   // double buffered
-    const int Ho = ST == 1 ? H + 3 - KS : H / ST, Wo = ST == 1 ? W + 3 - KS : W / ST;   // padding 1
+    const int Ho = ST == 1 ? L.H + 3 - KS : L.H / ST, Wo = ST == 1 ? L.W + 3 - KS : L.W / ST;   // padding 1
     const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + WTH - 1) / WTH;
-    const int blocks = (Cout / COB) * (Cin / CIB);
-    int per_block = (num_cus * wgrad_wgs_per_cu<COB, CIB, ST, KS>() + blocks - 1) / blocks;   // one round of resident workgroups: fewer atomics
-    const int n_tiles = tiles_x * tiles_y * N;
+    const int blocks = (L.Cout / COB) * (L.Cin / CIB);
+    int per_block = (ctx->num_cus * wgrad_wgs_per_cu<COB, CIB, ST, KS>() + blocks - 1) / blocks;   // one round of resident workgroups: fewer atomics
+    const int n_tiles = tiles_x * tiles_y * L.N;
     if (per_block > n_tiles) per_block = n_tiles;
     if (per_block < 1) per_block = 1;
-    auto kern = conv3x3_nhwc_wgrad_kernel<COB, CIB, MASKED, ST, false, KS>;
-    if constexpr (KS == 3) { if (sc1 || sc2) kern = conv3x3_nhwc_wgrad_kernel<COB, CIB, MASKED, ST, true, 3>; }
+    auto kern = conv3x3_nhwc_wgrad_kernel<COB, CIB, false, ST, KS>;
+    if constexpr (KS == 3) { if (L.tap_mask != 0x1ff) kern = conv3x3_nhwc_wgrad_kernel<COB, CIB, true, ST, 3>; }
     OCTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)per_block, (unsigned)blocks), dim3(CONV_THREADS), lds, stream, X, X2, C1, dY, dW, N, H, W, Ho, Wo, Cin,
-                       Cout, tiles_x, tiles_y, tap_mask, sc1, sh1, sc2, sh2, slope, zero16);
+    hipLaunchKernelGGL(kern, dim3((unsigned)per_block, (unsigned)blocks), dim3(CONV_THREADS), lds, L.stream, L.X, L.X2, L.C1, L.dY, L.dW, L.N, L.H, L.W, Ho, Wo,
+                       L.Cin, L.Cout, tiles_x, tiles_y, L.tap_mask, L.sc1, L.sh1, L.sc2, L.sh2, L.slope, L.zero16);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
-}
-
-template <int COB, int CIB, int ST = 1>
-int launch_wgrad(const unsigned short *X, const unsigned short *X2, int C1, const unsigned short *dY, float *dW, int N, int H, int W, int Cin,
-                 int Cout, int num_cus, int tap_mask, const float *sc1, const float *sh1, const float *sc2, const float *sh2, float slope,
-                 const unsigned short *zero16, hipStream_t stream) {
-    if (tap_mask != 0x1ff) return launch_wgrad_impl<COB, CIB, true, ST>(X, X2, C1, dY, dW, N, H, W, Cin, Cout, num_cus, tap_mask, sc1, sh1, sc2, sh2, slope, zero16, stream);
-    return launch_wgrad_impl<COB, CIB, false, ST>(X, X2, C1, dY, dW, N, H, W, Cin, Cout, num_cus, tap_mask, sc1, sh1, sc2, sh2, slope, zero16, stream);
 }
 
 }  // namespace
@@ -1579,83 +1589,67 @@ extern "C" int octa_conv3x3_nhwc_wgrad(octa_ctx *ctx, const octa_conv3x3_wgrad_a
     const int N = a->N, H = a->H, W = a->W, Cin = a->Cin, Cout = a->Cout, stride = a->stride, out_mode = a->out_mode;
     const float *d_scale1 = a->d_scale1, *d_shift1 = a->d_shift1, *d_scale2 = a->d_scale2, *d_shift2 = a->d_shift2;
     const float slope = a->slope;
-    if (!ctx || !d_x || !d_dy || !d_dw) { octa::set_error("octa_conv3x3_nhwc_wgrad: null pointer"); return -2; }
-    if (out_mode < OCTA_WGRAD_TAP_MAJOR || out_mode > OCTA_WGRAD_PARAM_SET) { octa::set_error("octa_conv3x3_nhwc_wgrad: out_mode %d is none of OCTA_WGRAD_*", out_mode); return -2; }
+    if (null_pointer(__func__, ctx, d_x, d_dy, d_dw) || bad_out_mode(__func__, out_mode)) return -2;
     tap_mask &= 0x1ff;
     if (tap_mask == 0) { octa::set_error("octa_conv3x3_nhwc_wgrad: empty tap mask"); return -2; }
-    if (N <= 0 || H <= 0 || W <= 0) { octa::set_error("octa_conv3x3_nhwc_wgrad: bad shape"); return -2; }
-    if (Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) { octa::set_error("octa_conv3x3_nhwc_wgrad: Cin and Cout must be multiples of 32 (got %d, %d)", Cin, Cout); return -2; }
+    if (bad_shape(__func__, N, H, W) || bad_channels(__func__, Cin, Cout)) return -2;
     if (!d_x2) C1 = Cin;
     if (C1 <= 0 || C1 > Cin || C1 % 32) { octa::set_error("octa_conv3x3_nhwc_wgrad: the input split must be a multiple of 32 inside the channel range"); return -2; }
-    hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    const unsigned short *X = static_cast<const unsigned short *>(d_x), *X2 = static_cast<const unsigned short *>(d_x2);
-    const unsigned short *dY = static_cast<const unsigned short *>(d_dy);
-    const unsigned short *z = zero_page(ctx);
-    if (!z) return -1;
+    WgradLaunch L;
+    L.zero16 = zero_page(ctx);
+    if (!L.zero16) return -1;
+    L.X = static_cast<const unsigned short *>(d_x), L.X2 = static_cast<const unsigned short *>(d_x2), L.dY = static_cast<const unsigned short *>(d_dy), L.dW = d_dw;
+    L.C1 = C1, L.N = N, L.H = H, L.W = W, L.Cin = Cin, L.Cout = Cout, L.tap_mask = tap_mask, L.out_mode = out_mode, L.stream = (hipStream_t)stream_;
+    L.sc1 = d_scale1, L.sh1 = d_shift1, L.sc2 = d_scale2, L.sh2 = d_shift2, L.slope = slope;
     const bool co64 = Cout % 64 == 0, ci64 = Cin % 64 == 0 && C1 % 64 == 0;   // a 64-channel block must not straddle the split
     if (!d_scale1 && !d_scale2 && (stride == 1 || (stride == 2 && H % 2 == 0 && W % 2 == 0))) {
-        // raw tiles + transposing reads (see conv3x3_nhwc_wgrad_tr_kernel)
-        if (stride == 1) {
-            if (co64 && ci64) return launch_wgrad_tr<64, 64>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
-            if (co64) return launch_wgrad_tr<64, 32>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
-            if (ci64) return launch_wgrad_tr<32, 64>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
-            return launch_wgrad_tr<32, 32>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
-        }
-        if (co64) return launch_wgrad_tr<64, 32, 2>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
-        return launch_wgrad_tr<32, 32, 2>(ctx, X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, z, stream, 1, 0, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
+        // the default: raw tiles + transposing reads (see conv3x3_nhwc_wgrad_tr_kernel)
+        if (stride == 2) return co64 ? launch_wgrad_tr<64, 32, 2>(ctx, L) : launch_wgrad_tr<32, 32, 2>(ctx, L);
+        if (co64) return ci64 ? launch_wgrad_tr<64, 64>(ctx, L) : launch_wgrad_tr<64, 32>(ctx, L);
+        return ci64 ? launch_wgrad_tr<32, 64>(ctx, L) : launch_wgrad_tr<32, 32>(ctx, L);
     }
     if (out_mode) { octa::set_error("octa_conv3x3_nhwc_wgrad: the parameter-layout output needs the transposing-read kernels (no normalise-on-load operands, even sizes at stride 2)"); return -2; }
     // every refusal comes before the first write: a refused call leaves d_dw as it was
     if (stride != 1 && stride != 2) { octa::set_error("octa_conv3x3_nhwc_wgrad: stride must be 1 or 2"); return -2; }
     if (stride == 2 && (H % 2 || W % 2)) { octa::set_error("octa_conv3x3_nhwc_wgrad: stride-2 layers need even input sizes"); return -2; }
-    OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 9 * (size_t)Cout * Cin, stream));
-    if (stride == 2) {
-        // two column-parity planes per halo row: 32 input channels per workgroup keep the double buffer inside the LDS
-        if (co64) return launch_wgrad<64, 32, 2>(X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, d_scale1, d_shift1, d_scale2, d_shift2, slope, z, stream);
-        return launch_wgrad<32, 32, 2>(X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, d_scale1, d_shift1, d_scale2, d_shift2, slope, z, stream);
-    }
-    if (co64 && ci64) return launch_wgrad<64, 64>(X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, d_scale1, d_shift1, d_scale2, d_shift2, slope, z, stream);
-    if (co64) return launch_wgrad<64, 32>(X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, d_scale1, d_shift1, d_scale2, d_shift2, slope, z, stream);
-    if (ci64) return launch_wgrad<32, 64>(X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, d_scale1, d_shift1, d_scale2, d_shift2, slope, z, stream);
-    return launch_wgrad<32, 32>(X, X2, C1, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, tap_mask, d_scale1, d_shift1, d_scale2, d_shift2, slope, z, stream);
+    // normalise-on-load operands: the register-staged kernel, which adds to a cleared d_dw with atomics
+    OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 9 * (size_t)Cout * Cin, L.stream));
+    // stride 2: two column-parity planes per halo row: 32 input channels per workgroup keep the double buffer inside the LDS
+    if (stride == 2) return co64 ? launch_wgrad<64, 32, 2>(ctx, L) : launch_wgrad<32, 32, 2>(ctx, L);
+    if (co64) return ci64 ? launch_wgrad<64, 64>(ctx, L) : launch_wgrad<64, 32>(ctx, L);
+    return ci64 ? launch_wgrad<32, 64>(ctx, L) : launch_wgrad<32, 32>(ctx, L);
 }
 
 // Weight gradient of octa_conv3x3_nhwc_fwd_pad: d_x [N][H][W][Cin], d_dy [N][H + 2 pad - 2][W + 2 pad - 2][Cout], stride 1; reflect = 1
 // (pad = 1): the input was mirrored at its borders (nn.ReflectionPad2d(1) in front of the convolution). out_mode as octa_conv3x3_nhwc_wgrad.
 extern "C" int octa_conv3x3_nhwc_wgrad_pad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cin, int Cout, int pad,
                                            int reflect, int out_mode, void *stream_) {
-    if (!ctx || !d_x || !d_dy || !d_dw) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: null pointer"); return -2; }
-    if (out_mode < OCTA_WGRAD_TAP_MAJOR || out_mode > OCTA_WGRAD_PARAM_SET) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: out_mode %d is none of OCTA_WGRAD_*", out_mode); return -2; }
-    if (N <= 0 || H <= 0 || W <= 0 || pad < 0 || pad > 2 || H + 2 * pad < 3 || W + 2 * pad < 3) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: bad shape"); return -2; }
-    if (reflect && (pad != 1 || H < 2 || W < 2)) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: reflection needs pad = 1 and an image of at least 2 x 2"); return -2; }
-    if (Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) { octa::set_error("octa_conv3x3_nhwc_wgrad_pad: Cin and Cout must be multiples of 32 (got %d, %d)", Cin, Cout); return -2; }
-    hipStream_t stream = (hipStream_t)stream_;
+    if (null_pointer(__func__, ctx, d_x, d_dy, d_dw) || bad_out_mode(__func__, out_mode)) return -2;
+    if (bad_shape(__func__, N, H, W) || bad_pad(__func__, H, W, pad, reflect) || bad_channels(__func__, Cin, Cout)) return -2;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    const unsigned short *z = zero_page(ctx);
-    if (!z) return -1;
-    const unsigned short *X = static_cast<const unsigned short *>(d_x), *dY = static_cast<const unsigned short *>(d_dy);
-    const bool co64 = Cout % 64 == 0, ci64 = Cin % 64 == 0;
-    if (co64 && ci64) return launch_wgrad_tr<64, 64>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
-    if (co64) return launch_wgrad_tr<64, 32>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
-    if (ci64) return launch_wgrad_tr<32, 64>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
-    return launch_wgrad_tr<32, 32>(ctx, X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0x1ff, z, stream, pad, reflect, out_mode ? d_dw : nullptr, out_mode == OCTA_WGRAD_PARAM_ADD);
+    WgradLaunch L;
+    L.zero16 = zero_page(ctx);
+    if (!L.zero16) return -1;
+    L.X = static_cast<const unsigned short *>(d_x), L.dY = static_cast<const unsigned short *>(d_dy), L.dW = d_dw;
+    L.C1 = Cin, L.N = N, L.H = H, L.W = W, L.Cin = Cin, L.Cout = Cout, L.pad = pad, L.reflect = reflect, L.out_mode = out_mode, L.stream = (hipStream_t)stream_;
+    const bool ci64 = Cin % 64 == 0;
+    if (Cout % 64 == 0) return ci64 ? launch_wgrad_tr<64, 64>(ctx, L) : launch_wgrad_tr<64, 32>(ctx, L);
+    return ci64 ? launch_wgrad_tr<32, 64>(ctx, L) : launch_wgrad_tr<32, 32>(ctx, L);
 }
 
 extern "C" int octa_conv4x4_nhwc_wgrad(octa_ctx *ctx, const void *d_x, const void *d_dy, float *d_dw, int N, int H, int W, int Cin, int Cout,
                                        void *stream_) {
-    if (!ctx || !d_x || !d_dy || !d_dw) { octa::set_error("octa_conv4x4_nhwc_wgrad: null pointer"); return -2; }
-    if (N <= 0 || H < 2 || W < 2) { octa::set_error("octa_conv4x4_nhwc_wgrad: bad shape"); return -2; }
-    if (Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) { octa::set_error("octa_conv4x4_nhwc_wgrad: Cin and Cout must be multiples of 32 (got %d, %d)", Cin, Cout); return -2; }
+    if (null_pointer(__func__, ctx, d_x, d_dy, d_dw) || bad_shape(__func__, N, H, W, H < 2 || W < 2) || bad_channels(__func__, Cin, Cout)) return -2;
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 16 * (size_t)Cout * Cin, stream));
-    const unsigned short *z = zero_page(ctx);
-    if (!z) return -1;
-    const unsigned short *X = static_cast<const unsigned short *>(d_x), *dY = static_cast<const unsigned short *>(d_dy);
-    if (Cout % 64 == 0 && Cin % 64 == 0)
-        return launch_wgrad_impl<64, 64, false, 1, 4>(X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0xffff, nullptr, nullptr, nullptr, nullptr, 0.f, z, stream);
-    return launch_wgrad_impl<32, 32, false, 1, 4>(X, nullptr, Cin, dY, d_dw, N, H, W, Cin, Cout, ctx->num_cus, 0xffff, nullptr, nullptr, nullptr, nullptr, 0.f, z, stream);
+    WgradLaunch L;
+    L.zero16 = zero_page(ctx);
+    if (!L.zero16) return -1;
+    L.X = static_cast<const unsigned short *>(d_x), L.dY = static_cast<const unsigned short *>(d_dy), L.dW = d_dw;
+    L.C1 = Cin, L.N = N, L.H = H, L.W = W, L.Cin = Cin, L.Cout = Cout, L.tap_mask = 0xffff, L.stream = stream;
+    return Cout % 64 == 0 && Cin % 64 == 0 ? launch_wgrad<64, 64, 1, 4>(ctx, L) : launch_wgrad<32, 32, 1, 4>(ctx, L);
 }
 
 // ---- 1x1 head with one output channel (UnetOutBlock, 32 -> 1 with bias): HBM-bound streaming kernels ----------

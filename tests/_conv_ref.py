@@ -47,11 +47,11 @@ D (chain()) counts dependent fp32 roundings behind one accumulator, read from th
 r = R_MFMA is the number of roundings one MFMA instruction may apply to an accumulator element. r = 16: one rounding to nearest per
 product, as a chain of fp32 fused multiply-adds would give; the hardware's own order inside an instruction is not documented here.
 
-THE DISPATCH, as read from the host code (fwd_dispatch, wgrad_dispatch). Two observations the mirror records:
-  * conv3x3_nhwc_kernel<BN, ST, false, *> (register-staged, EXTRA = false) cannot be reached from octa_conv3x3_nhwc_fwd: launch_conv is only
-    called with scale / shift given, which selects <BN, ST, true, true>. They are listed in UNREACHABLE, not in the instantiations to cover.
-  * conv3x3_nhwc_wgrad_kernel<.., XFORM = false, 3> is likewise only compiled: without scale / shift the entry point takes the
-    transposing-read kernels or refuses (odd sizes at stride 2).
+THE DISPATCH, as read from the host code (fwd_dispatch, wgrad_dispatch). The register-staged forward kernel conv3x3_nhwc_kernel<BN, ST> exists
+only in its normalise-on-load form (the names reg<BN,stST,extra,masked> below), launched when scale / shift are given; every other forward call
+takes the DMA-staged kernels. The register-staged weight gradient conv3x3_nhwc_wgrad_kernel exists only as xform=1,k3 (scale / shift given:
+normalise-on-load compiled in) and as k4 (the 4x4 taps, without it): without scale / shift the 3x3 entry point takes the transposing-read
+kernels or refuses (odd sizes at stride 2).
 """
 import functools
 from types import SimpleNamespace
@@ -175,11 +175,6 @@ def fwd_instantiations():
     s |= {"glds<64,st1,k3,th16>", "glds<64,st1,k3,th16,stats>", "glds<32,st1,k4,th8>", "glds<64,st1,k4,th8>", "s2t<32>"}
     s |= {f"reg<{bn},st{st},extra,masked>" for bn in (32, 64) for st in (1, 2)}
     return s
-
-
-UNREACHABLE = {f"reg<{bn},st{st},plain{m}>" for bn in (32, 64) for st in (1, 2) for m in ("", ",masked")} | \
-              {f"wgrad<{co},{ci},masked={m},st{st},xform=0,k3>" for (co, ci, st) in ((64, 64, 1), (64, 32, 1), (32, 64, 1), (32, 32, 1), (64, 32, 2), (32, 32, 2))
-               for m in (0, 1)}
 
 
 def wgrad_refusal(p, **x):
