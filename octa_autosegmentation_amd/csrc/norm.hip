@@ -1,14 +1,21 @@
-// norm.hip -- fused InstanceNorm2d(affine) + LeakyReLU, forward and backward, for NCHW activations in
-// bf16 or fp32 (statistics and affine parameters in fp32). Reference: the norm1/lrelu and norm2/lrelu pairs
-// of MONAI's UnetBasicBlock that DynUNet is made of (models/networks.py:6 imports it; restated in
-// octa_autosegmentation_amd/models/networks.py). torch runs this as batch-norm + a separate activation
-// pass (and, under autocast, extra casts); at 1216x1216 every pass over a 32-channel map moves 95 MB, so
-// the step is HBM-bound. Here: forward = 2 reads + 1 write of the plane, backward =
-// 2 x (x, dy) reads + 1 write, nothing else.
-//
-// A (b, c) plane is split over `splits` workgroups so that >= ~2 workgroups per CU are in flight even for
-// the 128-plane top level; kernel 1 leaves per-split partial sums, kernel 2 folds them (a few floats) and
-// streams the plane with 16-byte accesses.
+// norm.hip -- fused InstanceNorm2d(affine) + LeakyReLU, forward and backward (statistics and affine parameters in fp32). Reference: the norm1/lrelu
+// and norm2/lrelu pairs of MONAI's UnetBasicBlock that DynUNet is made of (models/networks.py:6 imports it; restated in
+// octa_autosegmentation_amd/models/networks.py). torch runs this as batch-norm + a separate activation pass (and, under autocast, extra casts); at
+// 1216x1216 every pass over a 32-channel map moves 95 MB, so the step is HBM-bound. Every kernel here is a streaming pass: forward =
+// 2 reads + 1 write of the activation, backward = 2 x (x, dy) reads + 1 write, nothing else. Five kernel families, in the order of the file; the
+// formulas they share are written once, in the device helpers below the vector type.
+//   1. NCHW, bf16 or fp32 (in_fwd_stats / _apply, in_bwd_stats / _apply): octa_instnorm_lrelu_fwd / _bwd, called by models/fused_ops.py for the
+//      channels-first networks and the fp32 inference passes. A (b, c) plane is split over `splits` workgroups so that >= ~2 workgroups per CU are
+//      in flight even for the 128-plane top level; the statistics kernel leaves per-split partial sums, the apply kernel folds them (a few doubles)
+//      and streams the plane with 16-byte accesses.
+//   2. NHWC bf16 (in_nhwc_stats<0 / 1>, in_nhwc_fwd_apply, in_nhwc_bwd_apply): octa_instnorm_lrelu_nhwc_fwd / _bwd, the norm layers of the MFMA
+//      convolution path (models/mfma_conv.py).
+//   3. Statistics only + lazy application (in_nhwc_finalize, scale_shift_lrelu_nhwc): octa_instnorm_nhwc_stats / octa_scale_shift_lrelu_nhwc, the
+//      normalise-on-load route of models/mfma_conv.py: the consuming convolution applies scale / shift while it loads.
+//   4. Statistics from the producing convolution's epilogue: the d_stat_partials (in_nhwc_fold_partials) and d_stat_slots (slot_sum, in the apply
+//      pass's prologue) sources of octa_instnorm_lrelu_nhwc_fwd.
+//   5. Last norm + 1x1 output convolution to one channel, fused (in_nhwc_head_fwd / _head_bwd_stats / _head_bwd_apply):
+//      octa_instnorm_lrelu_head1_nhwc_fwd / _bwd, the U-Net's last layer in models/mfma_conv.py.
 #include <type_traits>
 #include "common.h"
 #include <cstdlib>
@@ -45,6 +52,20 @@ template <> struct Vec<unsigned short> {  // bf16 bits
     __device__ static void st1(unsigned short *p, float v) { *p = down(v); }
 };
 
+// ---- the formulas, each once (NCHW and NHWC kernels alike) --------------------------------------------------------------------
+__device__ __forceinline__ float lrelu(float z, float slope) { return z > 0.f ? z : z * slope; }
+// gradient d through the LeakyReLU whose pre-activation is xh * wc + bc
+__device__ __forceinline__ float lrelu_gate(float xh, float wc, float bc, float d, float slope) { return (xh * wc + bc) > 0.f ? d : d * slope; }
+// input gradient of the normalisation: scale = wc * rstd, mg / mgx = the plane's means of g and of g * xhat
+__device__ __forceinline__ float norm_dx(float scale, float g, float mg, float xh, float mgx) { return scale * (g - mg - xh * mgx); }
+// (sum x, sum x^2) over hw elements -> mean and 1 / sqrt(var + eps), in double: E[x^2] - mean^2 may come out below zero by rounding
+__device__ __forceinline__ void mean_rstd_of(double sa, double sq, long hw, float eps, float &mean, float &rstd) {
+    const double mean_d = sa / (double)hw;
+    double var = sq / (double)hw - mean_d * mean_d;
+    if (var < 0) var = 0;
+    mean = (float)mean_d; rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
 __device__ __forceinline__ void block_reduce2(double &a, double &b, double *sh) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) { a += __shfl_xor(a, d, 64); b += __shfl_xor(b, d, 64); }
@@ -56,6 +77,7 @@ __device__ __forceinline__ void block_reduce2(double &a, double &b, double *sh) 
     for (int k = 0; k < NT / 64; k++) { a += sh[2 * k]; b += sh[2 * k + 1]; }
 }
 
+// ---- 1. NCHW, bf16 or fp32 -----------------------------------------------------------------------------------------------------
 // chunk [e0, e1) of plane p handled by split s
 __device__ __forceinline__ void chunk_of(long hw, int splits, int s, int vecn, long &e0, long &e1) {
     long per = ((hw + splits - 1) / splits + vecn - 1) / vecn * vecn;
@@ -102,10 +124,7 @@ __global__ void __launch_bounds__(NT) in_fwd_apply(const T *__restrict__ x, T *_
     const int s = blockIdx.x, c = (int)(plane % C);
     double a = 0, b = 0;
     for (int k = 0; k < splits; k++) { a += partial[(plane * splits + k) * 2]; b += partial[(plane * splits + k) * 2 + 1]; }
-    const double mean_d = a / (double)hw;
-    double var = b / (double)hw - mean_d * mean_d;
-    if (var < 0) var = 0;
-    const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var + (double)eps));
+    float mean, rstd; mean_rstd_of(a, b, hw, eps, mean, rstd);
     if (s == 0 && threadIdx.x == 0) { mean_out[plane] = mean; rstd_out[plane] = rstd; }
     // fp32: (x - mean) * g + b as torch evaluates it -- x * g - mean * g cancels in single precision where |mean| >> std; bf16: one fma
     constexpr bool F32 = std::is_same<T, float>::value;
@@ -120,14 +139,13 @@ __global__ void __launch_bounds__(NT) in_fwd_apply(const T *__restrict__ x, T *_
             float v[8];
             Vec<T>::load(px + i, v);
 #pragma unroll
-            for (int k = 0; k < Vec<T>::N; k++) { float z = F32 ? (v[k] - mean) * g + b0 : v[k] * g + sh; v[k] = z > 0.f ? z : z * slope; }
+            for (int k = 0; k < Vec<T>::N; k++) v[k] = lrelu(F32 ? (v[k] - mean) * g + b0 : v[k] * g + sh, slope);
             Vec<T>::store(py + i, v);
         }
     } else {
         for (long i = e0 + threadIdx.x; i < e1; i += NT) {
             const float xv = Vec<T>::ld1(px + i);
-            float z = F32 ? (xv - mean) * g + b0 : xv * g + sh;
-            Vec<T>::st1(py + i, z > 0.f ? z : z * slope);
+            Vec<T>::st1(py + i, lrelu(F32 ? (xv - mean) * g + b0 : xv * g + sh, slope));
         }
     }
 }
@@ -154,14 +172,14 @@ __global__ void __launch_bounds__(NT) in_bwd_stats(const T *__restrict__ x, cons
 #pragma unroll
             for (int k = 0; k < Vec<T>::N; k++) {
                 float xh = (v[k] - mu) * rs;
-                float g = (xh * wc + bc) > 0.f ? d[k] : d[k] * slope;
+                float g = lrelu_gate(xh, wc, bc, d[k], slope);
                 sg += g; sgx += g * xh;
             }
         }
     } else {
         for (long i = e0 + threadIdx.x; i < e1; i += NT) {
             float xh = (Vec<T>::ld1(px + i) - mu) * rs, d = Vec<T>::ld1(pd + i);
-            float g = (xh * wc + bc) > 0.f ? d : d * slope;
+            float g = lrelu_gate(xh, wc, bc, d, slope);
             sg += g; sgx += g * xh;
         }
     }
@@ -200,16 +218,14 @@ __global__ void __launch_bounds__(NT) in_bwd_apply(const T *__restrict__ x, cons
 #pragma unroll
             for (int k = 0; k < Vec<T>::N; k++) {
                 float xh = (v[k] - mu) * rs;
-                float g = (xh * wc + bc) > 0.f ? d[k] : d[k] * slope;
-                v[k] = k0 * (g - mg - xh * mgx);
+                v[k] = norm_dx(k0, lrelu_gate(xh, wc, bc, d[k], slope), mg, xh, mgx);
             }
             Vec<T>::store(po + i, v);
         }
     } else {
         for (long i = e0 + threadIdx.x; i < e1; i += NT) {
             float xh = (Vec<T>::ld1(px + i) - mu) * rs, d = Vec<T>::ld1(pd + i);
-            float g = (xh * wc + bc) > 0.f ? d : d * slope;
-            Vec<T>::st1(po + i, k0 * (g - mg - xh * mgx));
+            Vec<T>::st1(po + i, norm_dx(k0, lrelu_gate(xh, wc, bc, d, slope), mg, xh, mgx));
         }
     }
 }
@@ -222,6 +238,17 @@ int pick_splits(const octa_ctx *ctx, long planes, long hw) {
     if (s > max_by_size) s = (int)max_by_size;
     if (s > 64) s = 64;
     return s;
+}
+
+// clears the affine gradients that the backward apply kernels accumulate into with atomics (either may be NULL)
+int zero_affine_grads(float *d_dw, float *d_db, int C, hipStream_t stream) {
+    if (d_dw && d_db == d_dw + C) {                                   // allocated back to back by the host side: one fill
+        OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 2 * C, stream));
+    } else {
+        if (d_dw) OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * C, stream));
+        if (d_db) OCTA_HIP_CHECK(hipMemsetAsync(d_db, 0, sizeof(float) * C, stream));
+    }
+    return 0;
 }
 
 }  // namespace
@@ -237,13 +264,14 @@ extern "C" int octa_instnorm_lrelu_fwd(octa_ctx *ctx, const void *d_x, void *d_y
     if (ctx->r_tile_total.reserve(sizeof(double) * 2 * planes * splits)) return -1;
     double *partial = ctx->r_tile_total.as<double>();
     dim3 grid((unsigned)splits, (unsigned)planes);
-    if (dtype == 0) {
-        hipLaunchKernelGGL(in_fwd_stats<float>, grid, dim3(NT), 0, stream, (const float *)d_x, (long)hw, splits, partial);
-        hipLaunchKernelGGL(in_fwd_apply<float>, grid, dim3(NT), 0, stream, (const float *)d_x, (float *)d_y, d_w, d_b, (long)hw, C, splits, partial, slope, eps, d_mean, d_rstd);
-    } else if (dtype == 1) {
-        hipLaunchKernelGGL(in_fwd_stats<unsigned short>, grid, dim3(NT), 0, stream, (const unsigned short *)d_x, (long)hw, splits, partial);
-        hipLaunchKernelGGL(in_fwd_apply<unsigned short>, grid, dim3(NT), 0, stream, (const unsigned short *)d_x, (unsigned short *)d_y, d_w, d_b, (long)hw, C, splits, partial, slope, eps, d_mean, d_rstd);
-    } else { octa::set_error("octa_instnorm_lrelu_fwd: dtype must be 0 (f32) or 1 (bf16)"); return -2; }
+    auto launch = [&](auto t) {   // t: an element of the activations' type
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(in_fwd_stats<T>, grid, dim3(NT), 0, stream, (const T *)d_x, (long)hw, splits, partial);
+        hipLaunchKernelGGL(in_fwd_apply<T>, grid, dim3(NT), 0, stream, (const T *)d_x, (T *)d_y, d_w, d_b, (long)hw, C, splits, partial, slope, eps, d_mean, d_rstd);
+    };
+    if (dtype == 0) launch(float());
+    else if (dtype == 1) launch((unsigned short)0);
+    else { octa::set_error("octa_instnorm_lrelu_fwd: dtype must be 0 (f32) or 1 (bf16)"); return -2; }
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -259,24 +287,21 @@ extern "C" int octa_instnorm_lrelu_bwd(octa_ctx *ctx, const void *d_x, const voi
     if (ctx->r_tile_total.reserve(sizeof(double) * 2 * planes * splits)) return -1;
     double *partial = ctx->r_tile_total.as<double>();
     dim3 grid((unsigned)splits, (unsigned)planes);
-    if (d_dw && d_db == d_dw + C) {                                   // allocated back to back by the host side: one fill
-        OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 2 * C, stream));
-    } else {
-        if (d_dw) OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * C, stream));
-        if (d_db) OCTA_HIP_CHECK(hipMemsetAsync(d_db, 0, sizeof(float) * C, stream));
-    }
-    if (dtype == 0) {
-        hipLaunchKernelGGL(in_bwd_stats<float>, grid, dim3(NT), 0, stream, (const float *)d_x, (const float *)d_dy, d_w, d_b, d_mean, d_rstd, (long)hw, C, splits, slope, partial);
-        hipLaunchKernelGGL(in_bwd_apply<float>, grid, dim3(NT), 0, stream, (const float *)d_x, (const float *)d_dy, (float *)d_dx, d_w, d_b, d_mean, d_rstd, (long)hw, C, splits, slope, partial, d_dw, d_db);
-    } else if (dtype == 1) {
-        hipLaunchKernelGGL(in_bwd_stats<unsigned short>, grid, dim3(NT), 0, stream, (const unsigned short *)d_x, (const unsigned short *)d_dy, d_w, d_b, d_mean, d_rstd, (long)hw, C, splits, slope, partial);
-        hipLaunchKernelGGL(in_bwd_apply<unsigned short>, grid, dim3(NT), 0, stream, (const unsigned short *)d_x, (const unsigned short *)d_dy, (unsigned short *)d_dx, d_w, d_b, d_mean, d_rstd, (long)hw, C, splits, slope, partial, d_dw, d_db);
-    } else { octa::set_error("octa_instnorm_lrelu_bwd: dtype must be 0 (f32) or 1 (bf16)"); return -2; }
+    if (zero_affine_grads(d_dw, d_db, C, stream)) return -1;
+    auto launch = [&](auto t) {   // t: an element of the activations' type
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(in_bwd_stats<T>, grid, dim3(NT), 0, stream, (const T *)d_x, (const T *)d_dy, d_w, d_b, d_mean, d_rstd, (long)hw, C, splits, slope, partial);
+        hipLaunchKernelGGL(in_bwd_apply<T>, grid, dim3(NT), 0, stream, (const T *)d_x, (const T *)d_dy, (T *)d_dx, d_w, d_b, d_mean, d_rstd, (long)hw, C, splits, slope,
+                           partial, d_dw, d_db);
+    };
+    if (dtype == 0) launch(float());
+    else if (dtype == 1) launch((unsigned short)0);
+    else { octa::set_error("octa_instnorm_lrelu_bwd: dtype must be 0 (f32) or 1 (bf16)"); return -2; }
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-// ---- NHWC (channels-last) bf16 variants, for the MFMA convolution path (csrc/conv.hip) ------------------------
+// ---- 2. NHWC (channels-last) bf16, for the MFMA convolution path (csrc/conv.hip) ----------------------------------------------
 // Activations [B][HW][C] bf16, C a multiple of 8. A thread owns 8 consecutive channels (one 16-byte access) of a
 // strided set of pixels; per-channel partial sums meet in LDS, then one double atomicAdd per channel and block
 // into sums[b][c][2]. The apply kernels read the finished sums, derive scale / shift per channel into LDS and
@@ -290,6 +315,19 @@ __device__ __forceinline__ void nhwc_geometry(int C, int &cg, int &pl, int &npl)
     cg = threadIdx.x % groups;
     pl = threadIdx.x / groups;
     npl = NT / groups;
+}
+
+// pixels [p0, p1) of an image handled by split s
+__device__ __forceinline__ void pixel_range(long hw, int splits, int s, long &p0, long &p1) {
+    const long per = (hw + splits - 1) / splits;
+    p0 = (long)s * per;
+    p1 = p0 + per < hw ? p0 + per : hw;
+}
+
+// the per-group constants of the backward kernels, for channel c (one of the thread's eight) of image b: saved statistics, affine parameters (absent: 1, 0)
+__device__ __forceinline__ void load_consts(const float *mean, const float *rstd, const float *w, const float *bias, int b, int C, int c, float &mu,
+                                            float &rs, float &wc, float &bc) {
+    mu = mean[(long)b * C + c]; rs = rstd[(long)b * C + c]; wc = w ? w[c] : 1.f; bc = bias ? bias[c] : 0.f;
 }
 
 // sum over the slots of sums[nslot][.][2] at element e (sum, sum of squares): the loads of eight slots are issued together (index clamped,
@@ -309,6 +347,20 @@ __device__ __forceinline__ void slot_sum(const double *__restrict__ sums, long e
     }
 }
 
+// prologue of the forward apply passes, for channel c of image b: the sums of all slots -> mean / rstd (stored by split 0) -> scale / shift in LDS.
+// One slot with stride 0 = plain sums[B][C][2]; more = the slot form [nslot][B][C][2] of the producing convolution's epilogue (csrc/conv.hip,
+// octa_conv3x3_nhwc_fwd). The loop over c stays in the kernels: with a loop inside, a helper changes the device code
+__device__ __forceinline__ void scale_shift_to_lds(const double *sums, int nslot, long slot_stride, const float *w, const float *bias, long hw, int C,
+                                                   int b, int c, int s, float eps, float *mean_out, float *rstd_out, float (&s_g)[NHWC_MAXC],
+                                                   float (&s_sh)[NHWC_MAXC]) {
+    double sa, sq;
+    slot_sum(sums, (long)b * C + c, nslot, slot_stride, sa, sq);
+    float mean, rstd; mean_rstd_of(sa, sq, hw, eps, mean, rstd);
+    if (s == 0) { mean_out[(long)b * C + c] = mean; rstd_out[(long)b * C + c] = rstd; }
+    const float g = w ? w[c] * rstd : rstd;
+    s_g[c] = g; s_sh[c] = (bias ? bias[c] : 0.f) - mean * g;
+}
+
 // mode 0: (sum x, sum x^2); mode 1: (sum g, sum g*xhat) with g = dy * lrelu'(pre)
 template <int MODE>
 __global__ void __launch_bounds__(NT)
@@ -320,18 +372,14 @@ in_nhwc_stats(const unsigned short *__restrict__ x, const unsigned short *__rest
     int cg, pl, npl;
     nhwc_geometry(C, cg, pl, npl);
     const bool active = pl < npl && cg < C / 8;   // NT need not be a multiple of C/8
-    const long per = (hw + splits - 1) / splits;
-    const long p0 = (long)s * per, p1 = p0 + per < hw ? p0 + per : hw;
+    long p0, p1; pixel_range(hw, splits, s, p0, p1);
     float a[8], q[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) { a[k] = 0.f; q[k] = 0.f; }
     float mu[8], rs[8], wc[8], bc[8];
     if (MODE == 1 && active) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int c = cg * 8 + k;
-            mu[k] = mean[(long)b * C + c]; rs[k] = rstd[(long)b * C + c]; wc[k] = w ? w[c] : 1.f; bc[k] = bias ? bias[c] : 0.f;
-        }
+        for (int k = 0; k < 8; k++) load_consts(mean, rstd, w, bias, b, C, cg * 8 + k, mu[k], rs[k], wc[k], bc[k]);
     }
     if (active) {
         const unsigned short *px = x + ((long)b * hw) * C + cg * 8;
@@ -357,7 +405,7 @@ in_nhwc_stats(const unsigned short *__restrict__ x, const unsigned short *__rest
 #pragma unroll
                     for (int k = 0; k < 8; k++) {
                         const float xh = (v[u][k] - mu[k]) * rs[k];
-                        const float g = (xh * wc[k] + bc[k]) > 0.f ? d[u][k] : d[u][k] * slope;
+                        const float g = lrelu_gate(xh, wc[k], bc[k], d[u][k], slope);
                         a[k] += g; q[k] += g * xh;
                     }
             }
@@ -374,13 +422,13 @@ in_nhwc_stats(const unsigned short *__restrict__ x, const unsigned short *__rest
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
                     const float xh = (v[k] - mu[k]) * rs[k];
-                    const float g = (xh * wc[k] + bc[k]) > 0.f ? d[k] : d[k] * slope;
+                    const float g = lrelu_gate(xh, wc[k], bc[k], d[k], slope);
                     a[k] += g; q[k] += g * xh;
                 }
             }
         }
     }
-    // fold the pixel lanes of every channel group
+    // fold the pixel lanes of every channel group (in_nhwc_head_bwd_stats repeats it: as a shared helper it changed all three kernels' code)
 #pragma unroll
     for (int k = 0; k < 8; k++) { s_red[(threadIdx.x * 8 + k) * 2] = a[k]; s_red[(threadIdx.x * 8 + k) * 2 + 1] = q[k]; }
     __syncthreads();
@@ -399,27 +447,15 @@ in_nhwc_stats(const unsigned short *__restrict__ x, const unsigned short *__rest
 __global__ void __launch_bounds__(NT)
 in_nhwc_fwd_apply(const unsigned short *__restrict__ x, unsigned short *__restrict__ y, const float *__restrict__ w,
                   const float *__restrict__ bias, long hw, int C, int splits, const double *__restrict__ sums, float slope, float eps,
-                  float *__restrict__ mean_out, float *__restrict__ rstd_out, int b0, int nslot = 1, long slot_stride = 0) {
+                  float *__restrict__ mean_out, float *__restrict__ rstd_out, int b0, int nslot, long slot_stride) {
     __shared__ float s_g[NHWC_MAXC], s_sh[NHWC_MAXC];
     const int b = blockIdx.y + b0, s = blockIdx.x;
-    for (int c = threadIdx.x; c < C; c += NT) {
-        // nslot > 1: the sums come from the producing convolution's epilogue, spread over slots [nslot][B][C][2] (csrc/conv.hip, octa_conv3x3_nhwc_fwd)
-        double sa, sq;
-        slot_sum(sums, (long)b * C + c, nslot, slot_stride, sa, sq);
-        const double mean_d = sa / (double)hw;
-        double var = sq / (double)hw - mean_d * mean_d;
-        if (var < 0) var = 0;
-        const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var + (double)eps));
-        if (s == 0) { mean_out[(long)b * C + c] = mean; rstd_out[(long)b * C + c] = rstd; }
-        const float g = w ? w[c] * rstd : rstd;
-        s_g[c] = g; s_sh[c] = (bias ? bias[c] : 0.f) - mean * g;
-    }
+    for (int c = threadIdx.x; c < C; c += NT) scale_shift_to_lds(sums, nslot, slot_stride, w, bias, hw, C, b, c, s, eps, mean_out, rstd_out, s_g, s_sh);
     __syncthreads();
     int cg, pl, npl;
     nhwc_geometry(C, cg, pl, npl);
     if (pl >= npl) return;
-    const long per = (hw + splits - 1) / splits;
-    const long p0 = (long)s * per, p1 = p0 + per < hw ? p0 + per : hw;
+    long p0, p1; pixel_range(hw, splits, s, p0, p1);
     float g[8], sh[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) { g[k] = s_g[cg * 8 + k]; sh[k] = s_sh[cg * 8 + k]; }
@@ -433,7 +469,7 @@ in_nhwc_fwd_apply(const unsigned short *__restrict__ x, unsigned short *__restri
 #pragma unroll
         for (int u = 0; u < 4; u++) {
 #pragma unroll
-            for (int k = 0; k < 8; k++) { const float z = v[u][k] * g[k] + sh[k]; v[u][k] = z > 0.f ? z : z * slope; }
+            for (int k = 0; k < 8; k++) v[u][k] = lrelu(v[u][k] * g[k] + sh[k], slope);
             Vec<unsigned short>::store(py + (p + (long)u * npl) * C, v[u]);
         }
     }
@@ -441,7 +477,7 @@ in_nhwc_fwd_apply(const unsigned short *__restrict__ x, unsigned short *__restri
         float v[8];
         Vec<unsigned short>::load(px + p * C, v);
 #pragma unroll
-        for (int k = 0; k < 8; k++) { const float z = v[k] * g[k] + sh[k]; v[k] = z > 0.f ? z : z * slope; }
+        for (int k = 0; k < 8; k++) v[k] = lrelu(v[k] * g[k] + sh[k], slope);
         Vec<unsigned short>::store(py + p * C, v);
     }
 }
@@ -476,13 +512,12 @@ in_nhwc_bwd_apply(const unsigned short *__restrict__ x, const unsigned short *__
     int cg, pl, npl;
     nhwc_geometry(C, cg, pl, npl);
     if (pl >= npl) return;
-    const long per = (hw + splits - 1) / splits;
-    const long p0 = (long)s * per, p1 = p0 + per < hw ? p0 + per : hw;
+    long p0, p1; pixel_range(hw, splits, s, p0, p1);
     float mu[8], rs[8], wc[8], bc[8], mg[8], mgx[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const int c = cg * 8 + k;
-        mu[k] = mean[(long)b * C + c]; rs[k] = rstd[(long)b * C + c]; wc[k] = w ? w[c] : 1.f; bc[k] = bias ? bias[c] : 0.f;
+        load_consts(mean, rstd, w, bias, b, C, c, mu[k], rs[k], wc[k], bc[k]);
         mg[k] = s_mg[c]; mgx[k] = s_mgx[c];
     }
     const unsigned short *px = x + ((long)b * hw) * C + cg * 8, *pd = dy + ((long)b * hw) * C + cg * 8;
@@ -497,8 +532,7 @@ in_nhwc_bwd_apply(const unsigned short *__restrict__ x, const unsigned short *__
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 const float xh = (v[u][k] - mu[k]) * rs[k];
-                const float g = (xh * wc[k] + bc[k]) > 0.f ? d[u][k] : d[u][k] * slope;
-                v[u][k] = wc[k] * rs[k] * (g - mg[k] - xh * mgx[k]);
+                v[u][k] = norm_dx(wc[k] * rs[k], lrelu_gate(xh, wc[k], bc[k], d[u][k], slope), mg[k], xh, mgx[k]);
             }
             Vec<unsigned short>::store(po + (p + (long)u * npl) * C, v[u]);
         }
@@ -510,8 +544,7 @@ in_nhwc_bwd_apply(const unsigned short *__restrict__ x, const unsigned short *__
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const float xh = (v[k] - mu[k]) * rs[k];
-            const float g = (xh * wc[k] + bc[k]) > 0.f ? d[k] : d[k] * slope;
-            v[k] = wc[k] * rs[k] * (g - mg[k] - xh * mgx[k]);
+            v[k] = norm_dx(wc[k] * rs[k], lrelu_gate(xh, wc[k], bc[k], d[k], slope), mg[k], xh, mgx[k]);
         }
         Vec<unsigned short>::store(po + p * C, v);
     }
@@ -523,8 +556,7 @@ int nhwc_splits(const octa_ctx *ctx, int B, long hw) {
     // residual stages ran on 11 x B workgroups, 17 % of the CUs at B = 4; GAN-seg step 56.8 -> 55.4 ms, U-Net step unchanged;
     // profiles/r04_norm_min_pixels.log). For the planes of these networks the bound, not the batch size, decides the split count at
     // B <= 4, so an image's partial sums are formed alike alone and in a batch (tests/test_training_cli_gpu.py compares the two).
-    constexpr long min_px_env = 0L;
-    const long min_px = min_px_env > 0 ? min_px_env : (hw < 65536 ? 128 : 512);
+    const long min_px = hw < 65536 ? 128 : 512;
     const long by_size = hw / min_px > 0 ? hw / min_px : 1;
     if (s > by_size) s = by_size;
     if (s < 1) s = 1;
@@ -552,20 +584,28 @@ int nhwc_check(const char *who, int B, int C, int64_t hw) {
     return 0;
 }
 
-}  // namespace
+// what an NHWC entry point does first: null pointers, then the shape, then the device
+int nhwc_enter(const char *who, const octa_ctx *ctx, bool ptrs, int B, int C, int64_t hw, int (*check)(const char *, int, int, int64_t) = nhwc_check) {
+    if (!ctx || !ptrs) { octa::set_error("%s: null pointer", who); return -2; }
+    if (check(who, B, C, hw)) return -2;
+    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
+    return 0;
+}
 
-namespace {
+// (sum x, sum x^2) of the images [b0, b0 + grid.y) added into sums: in_nhwc_stats<0> reads no dy, affine parameters, saved statistics or slope
+void launch_x_stats(dim3 grid, hipStream_t stream, const unsigned short *x, long hw, int C, double *sums, int b0) {
+    hipLaunchKernelGGL(in_nhwc_stats<0>, grid, dim3(NT), 0, stream, x, (const unsigned short *)nullptr, (const float *)nullptr, (const float *)nullptr,
+                       (const float *)nullptr, (const float *)nullptr, hw, C, (int)grid.x, 0.f, sums, b0);
+}
 
+// ---- 3. statistics only + lazy application (normalise-on-load path of csrc/conv.hip) -------------------------------------------
 __global__ void __launch_bounds__(NT)
 in_nhwc_finalize(const double *__restrict__ sums, const float *__restrict__ w, const float *__restrict__ bias, long hw, int C, long total,
                  float eps, float *__restrict__ mean_out, float *__restrict__ rstd_out, float *__restrict__ scale, float *__restrict__ shift) {
     const long i = (long)blockIdx.x * NT + threadIdx.x;
     if (i >= total) return;
     const int c = (int)(i % C);
-    const double mean_d = sums[2 * i] / (double)hw;
-    double var = sums[2 * i + 1] / (double)hw - mean_d * mean_d;
-    if (var < 0) var = 0;
-    const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var + (double)eps));
+    float mean, rstd; mean_rstd_of(sums[2 * i], sums[2 * i + 1], hw, eps, mean, rstd);
     mean_out[i] = mean; rstd_out[i] = rstd;
     const float g = w ? w[c] * rstd : rstd;
     scale[i] = g;
@@ -579,8 +619,7 @@ scale_shift_lrelu_nhwc(const unsigned short *__restrict__ x, unsigned short *__r
     int cg, pl, npl;
     nhwc_geometry(C, cg, pl, npl);
     if (pl >= npl) return;
-    const long per = (hw + splits - 1) / splits;
-    const long p0 = (long)s * per, p1 = p0 + per < hw ? p0 + per : hw;
+    long p0, p1; pixel_range(hw, splits, s, p0, p1);
     float g[8], sh[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) { g[k] = scale[(long)b * C + cg * 8 + k]; sh[k] = shift[(long)b * C + cg * 8 + k]; }
@@ -590,7 +629,7 @@ scale_shift_lrelu_nhwc(const unsigned short *__restrict__ x, unsigned short *__r
         float v[8];
         Vec<unsigned short>::load(px + p * C, v);
 #pragma unroll
-        for (int k = 0; k < 8; k++) { const float z = v[k] * g[k] + sh[k]; v[k] = z > 0.f ? z : z * slope; }
+        for (int k = 0; k < 8; k++) v[k] = lrelu(v[k] * g[k] + sh[k], slope);
         Vec<unsigned short>::store(py + p * C, v);
     }
 }
@@ -599,15 +638,12 @@ scale_shift_lrelu_nhwc(const unsigned short *__restrict__ x, unsigned short *__r
 
 extern "C" int octa_instnorm_nhwc_stats(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_b, float *d_mean, float *d_rstd,
                                         float *d_scale, float *d_shift, int B, int C, int64_t hw, float eps, void *stream_) {
-    if (!ctx || !d_x || !d_mean || !d_rstd || !d_scale || !d_shift) { octa::set_error("octa_instnorm_nhwc_stats: null pointer"); return -2; }
-    if (nhwc_check("octa_instnorm_nhwc_stats", B, C, hw)) return -2;
+    if (int rc = nhwc_enter("octa_instnorm_nhwc_stats", ctx, d_x && d_mean && d_rstd && d_scale && d_shift, B, C, hw)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));   // pre-zeroed ring slot
     if (!sums) return -1;
     const int splits = nhwc_splits(ctx, B, hw);
-    hipLaunchKernelGGL(in_nhwc_stats<0>, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, static_cast<const unsigned short *>(d_x),
-                       (const unsigned short *)nullptr, d_w, d_b, (const float *)nullptr, (const float *)nullptr, (long)hw, C, splits, 0.f, sums, 0);
+    launch_x_stats(dim3((unsigned)splits, (unsigned)B), stream, static_cast<const unsigned short *>(d_x), (long)hw, C, sums, 0);
     const long total = (long)B * C;
     hipLaunchKernelGGL(in_nhwc_finalize, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, stream, sums, d_w, d_b, (long)hw, C, total, eps,
                        d_mean, d_rstd, d_scale, d_shift);
@@ -617,10 +653,8 @@ extern "C" int octa_instnorm_nhwc_stats(octa_ctx *ctx, const void *d_x, const fl
 
 extern "C" int octa_scale_shift_lrelu_nhwc(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_scale, const float *d_shift, int B, int C,
                                            int64_t hw, float slope, void *stream_) {
-    if (!ctx || !d_x || !d_y || !d_scale || !d_shift) { octa::set_error("octa_scale_shift_lrelu_nhwc: null pointer"); return -2; }
-    if (nhwc_check("octa_scale_shift_lrelu_nhwc", B, C, hw)) return -2;
+    if (int rc = nhwc_enter("octa_scale_shift_lrelu_nhwc", ctx, d_x && d_y && d_scale && d_shift, B, C, hw)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     const int splits = nhwc_splits(ctx, B, hw);
     hipLaunchKernelGGL(scale_shift_lrelu_nhwc, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, static_cast<const unsigned short *>(d_x),
                        static_cast<unsigned short *>(d_y), d_scale, d_shift, (long)hw, C, splits, slope);
@@ -628,7 +662,7 @@ extern "C" int octa_scale_shift_lrelu_nhwc(octa_ctx *ctx, const void *d_x, void 
     return 0;
 }
 
-// ---- forward, optionally with the statistics already accumulated by the producing convolution (csrc/conv.hip) ----------
+// ---- 4. forward, optionally with the statistics already accumulated by the producing convolution (csrc/conv.hip) ---------------
 namespace {
 
 // partials [B][tiles][C][2] float -> sums [B][C][2] double. Block = 8 tile lanes x 32 channels.
@@ -659,6 +693,7 @@ in_nhwc_fold_partials(const float *__restrict__ part, int tiles, int C, double *
 extern "C" int octa_instnorm_lrelu_nhwc_fwd(octa_ctx *ctx, const void *d_x, void *d_y, const float *d_w, const float *d_b, float *d_mean,
                                             float *d_rstd, int B, int C, int64_t hw, float slope, float eps, const float *d_stat_partials,
                                             int tiles, const double *d_stat_slots, int nslot, void *stream_) {
+    // the one entry point with a check between the null pointers and the shape: spelled out, so that errors are reported in the same order
     if (!ctx || !d_x || !d_y || !d_mean || !d_rstd) { octa::set_error("octa_instnorm_lrelu_nhwc_fwd: null pointer"); return -2; }
     if ((d_stat_partials && (d_stat_slots || tiles <= 0)) || (d_stat_slots && (nslot <= 0 || nslot > 1024))) {
         octa::set_error("octa_instnorm_lrelu_nhwc_fwd: one statistics source at most, with tiles >= 1 or 1..1024 slots");
@@ -679,7 +714,7 @@ extern "C" int octa_instnorm_lrelu_nhwc_fwd(octa_ctx *ctx, const void *d_x, void
         hipLaunchKernelGGL(in_nhwc_fold_partials, dim3((unsigned)((C + 31) / 32), (unsigned)B), dim3(NT), 0, stream, d_stat_partials, tiles, C, sums);
         const int splits = nhwc_splits(ctx, B, hw);
         hipLaunchKernelGGL(in_nhwc_fwd_apply, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, x, y, d_w, d_b, (long)hw, C, splits, sums, slope,
-                           eps, d_mean, d_rstd, 0);
+                           eps, d_mean, d_rstd, 0, 1, 0L);
     } else {
         double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));   // pre-zeroed ring slot
         if (!sums) return -1;
@@ -689,9 +724,8 @@ extern "C" int octa_instnorm_lrelu_nhwc_fwd(octa_ctx *ctx, const void *d_x, void
         dim3 grid((unsigned)splits, (unsigned)group);
         for (int b0 = 0; b0 < B; b0 += group) {
             if (b0 + group > B) grid.y = (unsigned)(B - b0);
-            hipLaunchKernelGGL(in_nhwc_stats<0>, grid, dim3(NT), 0, stream, x, (const unsigned short *)nullptr, d_w, d_b, (const float *)nullptr,
-                               (const float *)nullptr, (long)hw, C, splits, slope, sums, b0);
-            hipLaunchKernelGGL(in_nhwc_fwd_apply, grid, dim3(NT), 0, stream, x, y, d_w, d_b, (long)hw, C, splits, sums, slope, eps, d_mean, d_rstd, b0);
+            launch_x_stats(grid, stream, x, (long)hw, C, sums, b0);
+            hipLaunchKernelGGL(in_nhwc_fwd_apply, grid, dim3(NT), 0, stream, x, y, d_w, d_b, (long)hw, C, splits, sums, slope, eps, d_mean, d_rstd, b0, 1, 0L);
         }
     }
     OCTA_HIP_CHECK(hipGetLastError());
@@ -701,22 +735,13 @@ extern "C" int octa_instnorm_lrelu_nhwc_fwd(octa_ctx *ctx, const void *d_x, void
 extern "C" int octa_instnorm_lrelu_nhwc_bwd(octa_ctx *ctx, const void *d_x, const void *d_dy, const float *d_w, const float *d_b,
                                             const float *d_mean, const float *d_rstd, void *d_dx, float *d_dw, float *d_db, int B,
                                             int C, int64_t hw, float slope, void *stream_) {
-    if (!ctx || !d_x || !d_dy || !d_dx || !d_mean || !d_rstd) { octa::set_error("octa_instnorm_lrelu_nhwc_bwd: null pointer"); return -2; }
-    if (nhwc_check("octa_instnorm_lrelu_nhwc_bwd", B, C, hw)) return -2;
+    if (int rc = nhwc_enter("octa_instnorm_lrelu_nhwc_bwd", ctx, d_x && d_dy && d_dx && d_mean && d_rstd, B, C, hw)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));   // pre-zeroed ring slot
     if (!sums) return -1;
     const int group = nhwc_group(B, (size_t)hw * C * 2 * 2);   // two tensors (x, dy) are read twice
     const int bsum = group == B ? B : 0;                         // one launch covers the batch: gradients are stored, not accumulated
-    if (!bsum) {
-        if (d_dw && d_db == d_dw + C) {                               // allocated back to back by the host side: one fill
-            OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 2 * C, stream));
-        } else {
-            if (d_dw) OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * C, stream));
-            if (d_db) OCTA_HIP_CHECK(hipMemsetAsync(d_db, 0, sizeof(float) * C, stream));
-        }
-    }
+    if (!bsum && zero_affine_grads(d_dw, d_db, C, stream)) return -1;
     const int splits = nhwc_splits(ctx, group, hw);
     dim3 grid((unsigned)splits, (unsigned)group);
     const unsigned short *x = static_cast<const unsigned short *>(d_x), *dy = static_cast<const unsigned short *>(d_dy);
@@ -730,8 +755,7 @@ extern "C" int octa_instnorm_lrelu_nhwc_bwd(octa_ctx *ctx, const void *d_x, cons
     return 0;
 }
 
-// ---- statistics only + lazy application (normalise-on-load path of csrc/conv.hip) ---------------------------------
-// ---- last layer of the U-Net fused: InstanceNorm(affine) + LeakyReLU + 1x1 convolution to ONE channel ---------------
+// ---- 5. last layer of the U-Net fused: InstanceNorm(affine) + LeakyReLU + 1x1 convolution to ONE channel ---------------------
 // DynUNet's last UnetBasicBlock norm followed by UnetOutBlock (MONAI, models/networks.py:6; 32 -> 1 at 1216^2). Unfused, the
 // normalised tensor y (378 MB at B = 4) is written by the norm, read by the head, its gradient is written by the head's backward
 // and read twice by the norm's backward. Here y and dL/dy never exist in HBM: the head's dot product runs on the values the
@@ -744,27 +768,16 @@ namespace {
 __global__ void __launch_bounds__(NT)
 in_nhwc_head_fwd(const unsigned short *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias, long hw, int C, int splits,
                  const double *__restrict__ sums, float slope, float eps, float *__restrict__ mean_out, float *__restrict__ rstd_out,
-                 const float *__restrict__ headw, const float *__restrict__ headb, unsigned short *__restrict__ logits, int nslot = 1,
-                 long slot_stride = 0) {
+                 const float *__restrict__ headw, const float *__restrict__ headb, unsigned short *__restrict__ logits, int nslot,
+                 long slot_stride) {
     __shared__ float s_g[NHWC_MAXC], s_sh[NHWC_MAXC];
     const int b = blockIdx.y, s = blockIdx.x;
-    for (int c = threadIdx.x; c < C; c += NT) {
-        double sa, sq;                                   // nslot > 1: from the producing convolution's epilogue (octa_conv3x3_nhwc_fwd)
-        slot_sum(sums, (long)b * C + c, nslot, slot_stride, sa, sq);
-        const double mean_d = sa / (double)hw;
-        double var = sq / (double)hw - mean_d * mean_d;
-        if (var < 0) var = 0;
-        const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var + (double)eps));
-        if (s == 0) { mean_out[(long)b * C + c] = mean; rstd_out[(long)b * C + c] = rstd; }
-        const float g = w ? w[c] * rstd : rstd;
-        s_g[c] = g; s_sh[c] = (bias ? bias[c] : 0.f) - mean * g;
-    }
+    for (int c = threadIdx.x; c < C; c += NT) scale_shift_to_lds(sums, nslot, slot_stride, w, bias, hw, C, b, c, s, eps, mean_out, rstd_out, s_g, s_sh);
     __syncthreads();
     int cg, pl, npl;
     nhwc_geometry(C, cg, pl, npl);                 // host guarantees NT % (C / 8) == 0 and C / 8 a power of two <= 64
     const int groups = C / 8;
-    const long per = (hw + splits - 1) / splits;
-    const long p0 = (long)s * per, p1 = p0 + per < hw ? p0 + per : hw;
+    long p0, p1; pixel_range(hw, splits, s, p0, p1);
     float g[8], sh[8], hv[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) { g[k] = s_g[cg * 8 + k]; sh[k] = s_sh[cg * 8 + k]; hv[k] = headw[cg * 8 + k]; }
@@ -780,7 +793,7 @@ in_nhwc_head_fwd(const unsigned short *__restrict__ x, const float *__restrict__
         for (int u = 0; u < 4; u++) {
             dot[u] = 0.f;
 #pragma unroll
-            for (int k = 0; k < 8; k++) { const float z = v[u][k] * g[k] + sh[k]; dot[u] += (z > 0.f ? z : z * slope) * hv[k]; }
+            for (int k = 0; k < 8; k++) dot[u] += lrelu(v[u][k] * g[k] + sh[k], slope) * hv[k];
             for (int d = 1; d < groups; d <<= 1) dot[u] += __shfl_xor(dot[u], d, 64);
             if (cg == 0) pl_out[p + (long)u * npl] = octa_f2bf(dot[u] + hb);
         }
@@ -789,7 +802,7 @@ in_nhwc_head_fwd(const unsigned short *__restrict__ x, const float *__restrict__
         float v[8], dot = 0.f;
         Vec<unsigned short>::load(px + p * C, v);
 #pragma unroll
-        for (int k = 0; k < 8; k++) { const float z = v[k] * g[k] + sh[k]; dot += (z > 0.f ? z : z * slope) * hv[k]; }
+        for (int k = 0; k < 8; k++) dot += lrelu(v[k] * g[k] + sh[k], slope) * hv[k];
         for (int d = 1; d < groups; d <<= 1) dot += __shfl_xor(dot, d, 64);
         if (cg == 0) pl_out[p] = octa_f2bf(dot + hb);
     }
@@ -805,14 +818,14 @@ in_nhwc_head_bwd_stats(const unsigned short *__restrict__ x, const unsigned shor
     const int b = blockIdx.y, s = blockIdx.x;
     int cg, pl, npl;
     nhwc_geometry(C, cg, pl, npl);
-    const long per = (hw + splits - 1) / splits;
-    const long p0 = (long)s * per, p1 = p0 + per < hw ? p0 + per : hw;
+    long p0, p1; pixel_range(hw, splits, s, p0, p1);
     float a[8], q[8], t[8], sdl = 0.f, mu[8], rs[8], wc[8], bc[8], hv[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const int c = cg * 8 + k;
         a[k] = 0.f; q[k] = 0.f; t[k] = 0.f;
-        mu[k] = mean[(long)b * C + c]; rs[k] = rstd[(long)b * C + c]; wc[k] = w ? w[c] : 1.f; bc[k] = bias ? bias[c] : 0.f; hv[k] = headw[c];
+        load_consts(mean, rstd, w, bias, b, C, c, mu[k], rs[k], wc[k], bc[k]);
+        hv[k] = headw[c];
     }
     const unsigned short *px = x + ((long)b * hw) * C + cg * 8;
     const unsigned short *pd = dl + (long)b * hw;
@@ -825,10 +838,9 @@ in_nhwc_head_bwd_stats(const unsigned short *__restrict__ x, const unsigned shor
         for (int u = 0; u < 2; u++) {
 #pragma unroll
             for (int k = 0; k < 8; k++) {
-                const float xh = (v[u][k] - mu[k]) * rs[k], z = xh * wc[k] + bc[k];
-                const float dy = d[u] * hv[k];
-                const float gk = z > 0.f ? dy : dy * slope;
-                a[k] += gk; q[k] += gk * xh; t[k] += (z > 0.f ? z : z * slope) * d[u];
+                const float xh = (v[u][k] - mu[k]) * rs[k];
+                const float gk = lrelu_gate(xh, wc[k], bc[k], d[u] * hv[k], slope);
+                a[k] += gk; q[k] += gk * xh; t[k] += lrelu(xh * wc[k] + bc[k], slope) * d[u];
             }
             sdl += d[u];
         }
@@ -839,10 +851,9 @@ in_nhwc_head_bwd_stats(const unsigned short *__restrict__ x, const unsigned shor
         const float d = Vec<unsigned short>::up(pd[p]);
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            const float xh = (v[k] - mu[k]) * rs[k], z = xh * wc[k] + bc[k];
-            const float dy = d * hv[k];
-            const float gk = z > 0.f ? dy : dy * slope;
-            a[k] += gk; q[k] += gk * xh; t[k] += (z > 0.f ? z : z * slope) * d;
+            const float xh = (v[k] - mu[k]) * rs[k];
+            const float gk = lrelu_gate(xh, wc[k], bc[k], d * hv[k], slope);
+            a[k] += gk; q[k] += gk * xh; t[k] += lrelu(xh * wc[k] + bc[k], slope) * d;
         }
         sdl += d;
     }
@@ -895,13 +906,12 @@ in_nhwc_head_bwd_apply(const unsigned short *__restrict__ x, const unsigned shor
     __syncthreads();
     int cg, pl, npl;
     nhwc_geometry(C, cg, pl, npl);
-    const long per = (hw + splits - 1) / splits;
-    const long p0 = (long)s * per, p1 = p0 + per < hw ? p0 + per : hw;
+    long p0, p1; pixel_range(hw, splits, s, p0, p1);
     float mu[8], rs[8], wc[8], bc[8], mg[8], mgx[8], hv[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const int c = cg * 8 + k;
-        mu[k] = mean[(long)b * C + c]; rs[k] = rstd[(long)b * C + c]; wc[k] = w ? w[c] : 1.f; bc[k] = bias ? bias[c] : 0.f;
+        load_consts(mean, rstd, w, bias, b, C, c, mu[k], rs[k], wc[k], bc[k]);
         mg[k] = s_mg[c]; mgx[k] = s_mgx[c]; hv[k] = headw[c];
     }
     const unsigned short *px = x + ((long)b * hw) * C + cg * 8;
@@ -917,9 +927,7 @@ in_nhwc_head_bwd_apply(const unsigned short *__restrict__ x, const unsigned shor
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 const float xh = (v[u][k] - mu[k]) * rs[k];
-                const float dy = d[u] * hv[k];
-                const float gk = (xh * wc[k] + bc[k]) > 0.f ? dy : dy * slope;
-                v[u][k] = wc[k] * rs[k] * (gk - mg[k] - xh * mgx[k]);
+                v[u][k] = norm_dx(wc[k] * rs[k], lrelu_gate(xh, wc[k], bc[k], d[u] * hv[k], slope), mg[k], xh, mgx[k]);
             }
             Vec<unsigned short>::store(po + (p + (long)u * npl) * C, v[u]);
         }
@@ -931,9 +939,7 @@ in_nhwc_head_bwd_apply(const unsigned short *__restrict__ x, const unsigned shor
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const float xh = (v[k] - mu[k]) * rs[k];
-            const float dy = d * hv[k];
-            const float gk = (xh * wc[k] + bc[k]) > 0.f ? dy : dy * slope;
-            v[k] = wc[k] * rs[k] * (gk - mg[k] - xh * mgx[k]);
+            v[k] = norm_dx(wc[k] * rs[k], lrelu_gate(xh, wc[k], bc[k], d * hv[k], slope), mg[k], xh, mgx[k]);
         }
         Vec<unsigned short>::store(po + p * C, v);
     }
@@ -953,24 +959,22 @@ int head_check(const char *who, int B, int C, int64_t hw) {
 extern "C" int octa_instnorm_lrelu_head1_nhwc_fwd(octa_ctx *ctx, const void *d_x, const float *d_w, const float *d_b, const float *d_head_w,
                                                   const float *d_head_b, float *d_mean, float *d_rstd, void *d_logits, int B, int C, int64_t hw,
                                                   float slope, float eps, const double *d_slots, int nslot, void *stream_) {
-    if (!ctx || !d_x || !d_head_w || !d_mean || !d_rstd || !d_logits || (d_slots && nslot <= 0)) { octa::set_error("octa_instnorm_lrelu_head1_nhwc_fwd: null pointer"); return -2; }
-    if (head_check("octa_instnorm_lrelu_head1_nhwc_fwd", B, C, hw)) return -2;
+    if (int rc = nhwc_enter("octa_instnorm_lrelu_head1_nhwc_fwd", ctx, d_x && d_head_w && d_mean && d_rstd && d_logits && !(d_slots && nslot <= 0), B, C, hw,
+                            head_check))
+        return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     const int splits = nhwc_splits(ctx, B, hw);
     const dim3 grid((unsigned)splits, (unsigned)B);
     const unsigned short *x = static_cast<const unsigned short *>(d_x);
-    if (d_slots) {
-        hipLaunchKernelGGL(in_nhwc_head_fwd, grid, dim3(NT), 0, stream, x, d_w, d_b, (long)hw, C, splits, d_slots, slope, eps, d_mean, d_rstd, d_head_w,
-                           d_head_b, static_cast<unsigned short *>(d_logits), nslot, (long)B * C * 2);
-    } else {
-        double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));
-        if (!sums) return -1;
-        hipLaunchKernelGGL(in_nhwc_stats<0>, grid, dim3(NT), 0, stream, x, (const unsigned short *)nullptr, d_w, d_b, (const float *)nullptr,
-                           (const float *)nullptr, (long)hw, C, splits, slope, sums, 0);
-        hipLaunchKernelGGL(in_nhwc_head_fwd, grid, dim3(NT), 0, stream, x, d_w, d_b, (long)hw, C, splits, sums, slope, eps, d_mean, d_rstd, d_head_w,
-                           d_head_b, static_cast<unsigned short *>(d_logits));
+    const double *sums = d_slots;
+    if (!d_slots) {
+        double *own = static_cast<double *>(ctx->zeroed(sizeof(double) * 2 * (size_t)B * C, stream));
+        if (!own) return -1;
+        launch_x_stats(grid, stream, x, (long)hw, C, own, 0);
+        sums = own;
     }
+    hipLaunchKernelGGL(in_nhwc_head_fwd, grid, dim3(NT), 0, stream, x, d_w, d_b, (long)hw, C, splits, sums, slope, eps, d_mean, d_rstd, d_head_w, d_head_b,
+                       static_cast<unsigned short *>(d_logits), d_slots ? nslot : 1, d_slots ? (long)B * C * 2 : 0L);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -979,19 +983,14 @@ extern "C" int octa_instnorm_lrelu_head1_nhwc_bwd(octa_ctx *ctx, const void *d_x
                                                   const float *d_head_w, const float *d_mean, const float *d_rstd, void *d_dx, float *d_dw,
                                                   float *d_db, float *d_dhead_w, float *d_dhead_b, int B, int C, int64_t hw, float slope,
                                                   void *stream_) {
-    if (!ctx || !d_x || !d_dlogits || !d_head_w || !d_mean || !d_rstd || !d_dx || !d_dhead_w) { octa::set_error("octa_instnorm_lrelu_head1_nhwc_bwd: null pointer"); return -2; }
-    if (head_check("octa_instnorm_lrelu_head1_nhwc_bwd", B, C, hw)) return -2;
+    if (int rc = nhwc_enter("octa_instnorm_lrelu_head1_nhwc_bwd", ctx, d_x && d_dlogits && d_head_w && d_mean && d_rstd && d_dx && d_dhead_w, B, C, hw,
+                            head_check))
+        return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     double *sums = static_cast<double *>(ctx->zeroed(sizeof(double) * (2 * (size_t)B * C + C + 1), stream));
     if (!sums) return -1;
     double *hsums = sums + 2 * (size_t)B * C;
-    if (d_dw && d_db == d_dw + C) {
-        OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * 2 * C, stream));
-    } else {
-        if (d_dw) OCTA_HIP_CHECK(hipMemsetAsync(d_dw, 0, sizeof(float) * C, stream));
-        if (d_db) OCTA_HIP_CHECK(hipMemsetAsync(d_db, 0, sizeof(float) * C, stream));
-    }
+    if (zero_affine_grads(d_dw, d_db, C, stream)) return -1;
     const int splits = nhwc_splits(ctx, B, hw);
     const dim3 grid((unsigned)splits, (unsigned)B);
     const unsigned short *x = static_cast<const unsigned short *>(d_x), *dl = static_cast<const unsigned short *>(d_dlogits);
