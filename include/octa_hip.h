@@ -419,6 +419,14 @@ int octa_resize_bilinear(octa_ctx *ctx, const void *d_in, int in_dtype, int B, i
 int octa_resize_bilinear_bwd(octa_ctx *ctx, const float *d_dy, int B, int h, int w, int H, int W, float *d_dx, void *stream);
 int octa_flip_rot90_rotate(octa_ctx *ctx, const float *d_in, float *d_out, int B, int N, const float *d_angle, const int *d_rot_k,
                            const int *d_flip, float threshold, int use_threshold, void *stream);
+/* octa_flip_rot90_rotate for a window only -- RandCropOrPadd behind RandRotated (reference data/data_transforms.py:543-585; the Giarratano
+ * set-up crops 1216 -> 360): d_out is float32 [B][out_h][out_w], and its pixel (y, x) of image b is pixel (Y, X) = (d_oy[b] + y, d_ox[b] + x)
+ * of what octa_flip_rot90_rotate writes for the same inputs, bit for bit. Where (Y, X) lies outside [0, N)^2 (negative offsets: the pad
+ * case) the value is 0, and the threshold, if on, is applied to that 0 too (the reference pads before AsDiscreted). d_oy / d_ox: int32 [B] on
+ * the device. B, N, out_h, out_w in 1..65535; out must not alias in; nothing outside the window is written. */
+int octa_flip_rot90_rotate_window(octa_ctx *ctx, const float *d_in, float *d_out, int B, int N, const float *d_angle, const int *d_rot_k,
+                                  const int *d_flip, float threshold, int use_threshold, int out_h, int out_w, const int *d_oy,
+                                  const int *d_ox, void *stream);
 
 /* ---- the augmentation of Menten et al. (MICCAI 2022), the reference's comparison baseline (csrc/menten.hip) --------------------
  * MentenAugmentationd (reference data/data_transforms.py:44-325) = BinomialVesselNoised -> AddVitreousFloater -> AddMotionArtifact on samples

@@ -110,6 +110,8 @@ SIGNATURES = {
     "octa_resize_bilinear": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "octa_resize_bilinear_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "octa_flip_rot90_rotate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int, c_void_p]),
+    "octa_flip_rot90_rotate_window": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int, c_int, c_int,
+                                              c_void_p, c_void_p, c_void_p]),
     "octa_remove_small_objects": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint8, c_void_p, c_void_p]),
     "octa_cc3d_filter": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint8, c_void_p, c_void_p, c_void_p]),
     "octa_skeletonize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),

@@ -126,6 +126,42 @@ rotate_kernel(const float *__restrict__ in, float *__restrict__ out, int N, cons
     out[((size_t)b * N + Y) * N + X] = v;
 }
 
+// rotate_kernel for a window only (RandCropOrPadd behind RandRotated, reference data/data_transforms.py:543-585): out is [B][out_h][out_w] and
+// its pixel (y, x) of image b is pixel (Y, X) = (oy[b] + y, ox[b] + x) of what rotate_kernel writes; outside [0, N)^2 (negative offsets: the
+// pad case) the value is 0, and the threshold sees that 0 as well (the reference pads before AsDiscreted). The expressions are
+// rotate_kernel's own, in its form: the two kernels agree bit for bit. One thread per output pixel, nothing written outside the window.
+__global__ void __launch_bounds__(256)
+rotate_window_kernel(const float *__restrict__ in, float *__restrict__ out, int N, const float *__restrict__ angle, const int *__restrict__ rot_k,
+                     const int *__restrict__ flip, float threshold, int use_threshold, int out_h, int out_w, const int *__restrict__ oy,
+                     const int *__restrict__ ox) {
+    const int b = blockIdx.z, y = blockIdx.y, x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= out_w) return;
+    const long Yl = (long)oy[b] + y, Xl = (long)ox[b] + x;        // the offsets are the caller's device data: no int overflow on a wild one
+    float v = 0.f;
+    if (Yl >= 0 && Yl < N && Xl >= 0 && Xl < N) {
+        const int Y = (int)Yl, X = (int)Xl;
+        const float c = cosf(angle[b]), s = sinf(angle[b]);
+        // affine_grid base coordinates: (2i + 1) / N - 1
+        const float gx = (2.f * (float)X + 1.f) / (float)N - 1.f, gy = (2.f * (float)Y + 1.f) / (float)N - 1.f;
+        const float sx = c * gx - s * gy, sy = s * gx + c * gy;
+        // grid_sample unnormalise (align_corners = False): ((coord + 1) * N - 1) / 2
+        const float fx = ((sx + 1.f) * (float)N - 1.f) * 0.5f, fy = ((sy + 1.f) * (float)N - 1.f) * 0.5f;
+        const float x0f = floorf(fx), y0f = floorf(fy);
+        const int x0 = (int)x0f, y0 = (int)y0f;
+        const float tx = fx - x0f, ty = fy - y0f;
+        const float *img = in + (size_t)b * N * N;
+        const int k = rot_k ? rot_k[b] : 0, fl = flip ? flip[b] : 0;
+        // grid_sample's weights: nw = (x1 - x)(y1 - y), ne = (x - x0)(y1 - y), sw = (x1 - x)(y - y0), se = (x - x0)(y - y0)
+        const float nw = (1.f - tx) * (1.f - ty), ne = tx * (1.f - ty), sw = (1.f - tx) * ty, se = tx * ty;
+        v = tap(img, N, y0, x0, k, fl) * nw;
+        v += tap(img, N, y0, x0 + 1, k, fl) * ne;
+        v += tap(img, N, y0 + 1, x0, k, fl) * sw;
+        v += tap(img, N, y0 + 1, x0 + 1, k, fl) * se;
+    }
+    if (use_threshold) v = v >= threshold ? 1.f : 0.f;
+    out[((size_t)b * out_h + y) * out_w + x] = v;
+}
+
 // ---- noise model of the GAN configs (reference data/data_transforms.py:25-42 SpeckleBrightnesd, :498-516 AddRandomBackgroundNoised) ----
 // Both are streaming, HBM-bound maps over [B][H][W] float32 images; the random numbers are the reference's own streams (numpy's
 // global uniform stream for the background factor, torch's CPU generator for the speckle grid), drawn on the host and passed in.
@@ -252,6 +288,22 @@ extern "C" int octa_flip_rot90_rotate(octa_ctx *ctx, const float *d_in, float *d
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     dim3 grid((unsigned)((N + 255) / 256), (unsigned)N, (unsigned)B);
     hipLaunchKernelGGL(rotate_kernel, grid, dim3(256), 0, stream, d_in, d_out, N, d_angle, d_rot_k, d_flip, threshold, use_threshold);
+    OCTA_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int octa_flip_rot90_rotate_window(octa_ctx *ctx, const float *d_in, float *d_out, int B, int N, const float *d_angle, const int *d_rot_k,
+                                             const int *d_flip, float threshold, int use_threshold, int out_h, int out_w, const int *d_oy,
+                                             const int *d_ox, void *stream_) {
+    if (!ctx || !d_in || !d_out || !d_angle || !d_oy || !d_ox || B <= 0 || N <= 0 || out_h <= 0 || out_w <= 0 || B > 65535 || N > 65535 ||
+        out_h > 65535 || out_w > 65535 || d_in == d_out) {
+        octa::set_error("octa_flip_rot90_rotate_window: bad arguments"); return -2;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    OCTA_HIP_CHECK(hipSetDevice(ctx->device));
+    dim3 grid((unsigned)((out_w + 255) / 256), (unsigned)out_h, (unsigned)B);
+    hipLaunchKernelGGL(rotate_window_kernel, grid, dim3(256), 0, stream, d_in, d_out, N, d_angle, d_rot_k, d_flip, threshold, use_threshold, out_h, out_w,
+                       d_oy, d_ox);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }

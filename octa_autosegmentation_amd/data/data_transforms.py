@@ -7,7 +7,7 @@ Two groups:
 * the reference's OWN transforms on the hot path -- LoadGraphAndFilterByRandomRadiusd (:358-387), ToGrayScaled (:389-400),
   SpeckleBrightnesd (:25-42), AddRandomBackgroundNoised (:498-516), ImageToImageTranslationd (:327-356), and the comparison baseline
   MentenAugmentationd with its parts BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact (:44-325), and the paper's own noise
-  model NoiseModeld with RandomDecreaseResolutiond (:435-496);
+  model NoiseModeld with RandomDecreaseResolutiond (:435-496), and RandCropOrPadd (:543-585), the random crop of the Giarratano set-up;
 * the MONAI transforms those configs name (LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, RandFlipd, RandRotate90d,
   RandRotated, Rotate90d, Flipd, AsDiscreted, CastToTyped; post-processing: Activations, AsDiscrete, RemoveSmallObjects,
   KeepLargestConnectedComponent, CastToType; RemoveOuterNoise is the reference's own, :418-432), restated from MONAI's documented behaviour. MONAI is neither in the image nor under /root/reference:
@@ -572,6 +572,56 @@ class RandomDecreaseResolutiond(MapTransform):
         return data
 
 
+class RandCropOrPadd(MapTransform):
+    """Random crop or zero pad by a random zoom factor (reference :543-585; the Giarratano set-up crops 1216 -> 360 with both factors 0.2965),
+    restated literally. Every call draws `random.uniform(0, 1)` once from the global `random`; nothing else happens unless it is `< prob`.
+    Then `factor = random.uniform(min_factor, max_factor)`:
+      factor < 1: at the FIRST key only, s_x = int(shape[1] * factor), s_y = int(shape[2] * factor), then randint(0, shape[1] - s_x), then
+        randint(0, shape[2] - s_y) (rows first); every later key takes the same two slices whatever its own shape: d[:, slice_x, slice_y];
+      factor > 1, per key and without draws: a float32 zero frame [C, int(H * factor), int(W * factor)] on the tensor's device with the input
+        copied in at (frame - size) // 2 per axis -- float32 whatever the input's dtype (the reference's frame is torch.zeros on the CPU);
+      factor == 1: unchanged.
+    A missing key raises KeyError, as the reference's indexing does. Slices and copies only, on CPU and device tensors alike. `offsets` keeps the
+    (start_x, start_y) of the last crop, None after any other call (read by the tests and the fused chain's comparison)."""
+
+    def __init__(self, keys, prob=0.1, min_factor=1, max_factor=1) -> None:
+        super().__init__(keys)
+        self.prob = prob
+        self.min_factor = min_factor
+        self.max_factor = max_factor
+        self.offsets = None
+
+    def rng_streams(self, has_background=True):
+        return {"python"}
+
+    def __call__(self, data):
+        self.offsets = None
+        data = dict(data)
+        if _py_random.uniform(0, 1) < self.prob:
+            factor = _py_random.uniform(self.min_factor, self.max_factor)
+            slice_x = slice_y = None
+            for k in self.keys:
+                d = data[k]
+                if factor < 1:
+                    if slice_x is None:
+                        s_x = int(d.shape[1] * factor)
+                        s_y = int(d.shape[2] * factor)
+                        start_x = _py_random.randint(0, d.shape[1] - s_x)
+                        start_y = _py_random.randint(0, d.shape[2] - s_y)
+                        slice_x = slice(start_x, start_x + s_x)
+                        slice_y = slice(start_y, start_y + s_y)
+                        self.offsets = (start_x, start_y)
+                    d = d[:, slice_x, slice_y]
+                elif factor > 1:
+                    frame = torch.zeros((d.shape[0], int(d.shape[1] * factor), int(d.shape[2] * factor)), dtype=torch.float32, device=d.device)
+                    start_x = (frame.shape[1] - d.shape[1]) // 2
+                    start_y = (frame.shape[2] - d.shape[2]) // 2
+                    frame[:, start_x:start_x + d.shape[1], start_y:start_y + d.shape[2]] = d.clone()
+                    d = frame
+                data[k] = d
+        return data
+
+
 class ImageToImageTranslationd(MapTransform):
     """Frozen-generator contrast adaptation (reference :327-356) -- on the GPU (the reference runs resnetGenerator9 inside
     CPU loader workers: 6.1 s per image). `model` may be passed directly; otherwise resnetGenerator9 weights
@@ -976,7 +1026,7 @@ class AsChannelLast:
 
 TRANSFORMS = {c.__name__: c for c in (
     LoadGraphAndFilterByRandomRadiusd, ToGrayScaled, SpeckleBrightnesd, AddRandomBackgroundNoised, ImageToImageTranslationd,
-    BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact, MentenAugmentationd, NoiseModeld, RandomDecreaseResolutiond,
+    BinomialVesselNoised, AddVitreousFloater, AddMotionArtifact, MentenAugmentationd, NoiseModeld, RandomDecreaseResolutiond, RandCropOrPadd,
     LoadImaged, ScaleIntensityd, EnsureChannelFirstd, Resized, Flipd, RandFlipd, Rotate90d, RandRotate90d, RandRotated, AsDiscreted,
     CastToTyped, SelectSlice, Activations, AsDiscrete, RemoveSmallObjects, KeepLargestConnectedComponent, RemoveOuterNoise, Resize, CastToType,
     AsChannelLast)}

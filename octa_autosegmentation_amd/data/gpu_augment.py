@@ -10,7 +10,11 @@ decisions are drawn on the host from one numpy RandomState in the order MONAI's 
 (flip: rand() < p; rot90: rand() < p, then randint(3) + 1; rotate: rand() < p, then uniform(-r, r)), image and label of a
 sample share them. MONAI is not installed here: its per-transform random streams are not reproduced (parity unpinned),
 the geometry is pinned against the torch ops MONAI delegates to (tests/test_augment_gpu.py).
+The Giarratano set-up adds the reference's RandCropOrPadd behind RandRotated (configs/config_ves_seg-S_Giarratano.yml: 1216 -> 360): the
+rotate kernel's window form computes the kept pixels only, bit for bit those of the full frame (tests/test_crop_gpu.py).
 """
+
+import random as _py_random
 
 import numpy as np
 import torch
@@ -63,6 +67,19 @@ def flip_rot90_rotate(x, angle, rot_k=None, flip=None, threshold=None):
     return out
 
 
+def flip_rot90_rotate_window(x, angle, rot_k, flip, threshold, size, oy, ox):
+    """The window [oy[b] : oy[b] + size[0], ox[b] : ox[b] + size[1]] of flip_rot90_rotate(x, angle, rot_k, flip, threshold), bit for bit, computed
+    alone (RandCropOrPadd behind RandRotated): x CUDA float32 [B,N,N]; oy / ox int32 [B] on the device; what lies outside [0, N)^2 is 0
+    before the threshold (negative offsets: the pad case). -> float32 [B, size[0], size[1]]."""
+    assert x.is_cuda and x.dim() == 3 and x.shape[1] == x.shape[2] and x.dtype == torch.float32 and x.is_contiguous()
+    for o in (oy, ox):
+        assert o.is_cuda and o.dtype == torch.int32 and o.shape == (x.shape[0],) and o.is_contiguous()
+    out = torch.empty((x.shape[0], int(size[0]), int(size[1])), dtype=torch.float32, device=x.device)
+    _native.launch("octa_flip_rot90_rotate_window", x.device, x, out, x.shape[0], x.shape[1], angle, rot_k, flip,
+                   float(threshold if threshold is not None else 0.0), 0 if threshold is None else 1, out.shape[1], out.shape[2], oy, ox)
+    return out
+
+
 def background_noise(img, noise, u, out_dtype=torch.float64):
     """AddRandomBackgroundNoised on device tensors of equal shape: img / noise float32, u float64 (numpy's uniform factors).
     Returns max(img, noise * u) as float64 (the reference's promoted dtype) or float32."""
@@ -90,6 +107,7 @@ class GpuSegAugmentation:
     def __init__(self, aug_config, seed=None):
         self.size, self.flip_p, self.rot90_p, self.rot_p, self.rot_range, self.threshold = None, 0.0, 0.0, 0.0, 0.0, None
         self.scale = None
+        self.crop = None                 # RandCropOrPadd: (prob, min_factor, max_factor)
         for d in aug_config:
             name = d["name"]
             if name in ("LoadGraphAndFilterByRandomRadiusd", "EnsureChannelFirstd", "CastToTyped"):
@@ -112,6 +130,10 @@ class GpuSegAugmentation:
                 self.rot_p, self.rot_range = float(d.get("prob", 0.1)), float(d.get("range_x", 0.0))
             elif name == "AsDiscreted":
                 self.threshold = float(d["threshold"])
+            elif name == "RandCropOrPadd":
+                if self.crop is not None:
+                    raise NotImplementedError("RandCropOrPadd: the GPU augmentation chain takes one entry")
+                self.crop = (d.get("prob", 0.1), d.get("min_factor", 1), d.get("max_factor", 1))
             else:
                 raise NotImplementedError(f"transform {name} is not part of the GPU augmentation chain")
         # one generator PER random transform, all seeded alike -- what get_data_augmentations does with MONAI's Randomizable objects
@@ -135,6 +157,25 @@ class GpuSegAugmentation:
                 self.R_rot.uniform(low=0.0, high=0.0)
         return flip, k, ang
 
+    def draw_crop(self, shape):
+        """RandCropOrPadd's draws for ONE sample whose first key has the spatial `shape`, from the global `random` in the transform's order
+        (data_transforms.RandCropOrPadd). -> (out_h, out_w, oy, ox): the window of the rotated frame; a pad is a window with negative offsets;
+        not applied / factor 1 is the whole frame."""
+        prob, lo, hi = self.crop
+        H, W = int(shape[0]), int(shape[1])
+        if not _py_random.uniform(0, 1) < prob:
+            return H, W, 0, 0
+        factor = _py_random.uniform(lo, hi)
+        if factor < 1:
+            s_x, s_y = int(H * factor), int(W * factor)
+            oy = _py_random.randint(0, H - s_x)
+            ox = _py_random.randint(0, W - s_y)
+            return s_x, s_y, oy, ox
+        if factor > 1:
+            s_x, s_y = int(H * factor), int(W * factor)
+            return s_x, s_y, -((s_x - H) // 2), -((s_y - W) // 2)
+        return H, W, 0, 0
+
     def _scale_map(self, x):
         if self.scale is None:
             return None, None
@@ -147,19 +188,36 @@ class GpuSegAugmentation:
         mul = torch.where(span > 0, (hi - lo) / span, torch.zeros_like(span))     # MONAI: a constant image maps to minv
         return mul.contiguous(), (lo - mn * mul).contiguous()
 
-    def __call__(self, image, label):
-        """image, label: CUDA uint8 / float32 [B,h,w] (rasteriser output). -> dict(image, label) float32 [B,1,H,W]."""
+    def __call__(self, image, label, windows=None):
+        """image, label: CUDA uint8 / float32 [B,h,w] (rasteriser output). -> dict(image, label) float32 [B,1,H,W]. With a RandCropOrPadd entry
+        only the windows are computed (octa_flip_rot90_rotate_window): `windows` = one draw_crop() result per sample, all of one size (None:
+        drawn here, sample by sample) -> [B,1,out_h,out_w], the offsets in params["crop_oy"] / ["crop_ox"]."""
         B = image.shape[0]
         flip, k, ang = self.draw(B)
         dev = image.device
         flip_t, k_t, ang_t = (torch.from_numpy(a).to(dev) for a in (flip, k, ang))
+        params = dict(flip=flip, rot_k=k, angle=ang)
+        if self.crop is not None:
+            frame = self.size or list(image.shape[1:])           # the first key's shape after Resized: RandCropOrPadd takes its slices from it
+            if (self.size or list(label.shape[1:])) != frame:
+                raise NotImplementedError("RandCropOrPadd on the GPU augmentation chain: image and label need one size in front of the crop")
+            if windows is None:
+                windows = [self.draw_crop(frame) for _ in range(B)]
+            if len(windows) != B or len({tuple(w[:2]) for w in windows}) != 1:
+                raise ValueError(f"RandCropOrPadd: a mini-batch is stacked from windows of one size, got {sorted({tuple(w[:2]) for w in windows})}")
+            oy, ox = (np.array([w[i] for w in windows], dtype=np.int32) for i in (2, 3))
+            oy_t, ox_t = torch.from_numpy(oy).to(dev), torch.from_numpy(ox).to(dev)
+            params.update(crop_oy=oy, crop_ox=ox)
         out = {}
         for key, x, thr in (("image", image, None), ("label", label, self.threshold)):
             mul, add = self._scale_map(x)
             size = self.size or list(x.shape[1:])
             y = resize_bilinear(x.contiguous(), size, mul, add)
-            out[key] = flip_rot90_rotate(y, ang_t, k_t, flip_t, thr).unsqueeze(1)
-        out["params"] = dict(flip=flip, rot_k=k, angle=ang)
+            if self.crop is None:
+                out[key] = flip_rot90_rotate(y, ang_t, k_t, flip_t, thr).unsqueeze(1)
+            else:
+                out[key] = flip_rot90_rotate_window(y, ang_t, k_t, flip_t, thr, windows[0][:2], oy_t, ox_t).unsqueeze(1)
+        out["params"] = params
         return out
 
 

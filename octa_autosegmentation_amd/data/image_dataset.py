@@ -66,17 +66,30 @@ class FusedGraphSegBatches:
     graph loader without dropout, then ScaleIntensityd, EnsureChannelFirstd, Resized (bilinear), RandFlipd (both axes), RandRotate90d,
     RandRotated (zeros padding), AsDiscreted on the label, CastToTyped: a whole mini-batch is rendered by two rasteriser launch
     sequences (image and label resolution) and augmented by two streaming kernels per tensor (data/gpu_augment.py) instead of a
-    dozen small torch ops per sample and key. Takes the decisions of the generic per-sample transforms for the same seed."""
+    dozen small torch ops per sample and key. Takes the decisions of the generic per-sample transforms for the same seed.
+    One RandCropOrPadd entry may stand behind RandRotated (configs/config_ves_seg-S_Giarratano.yml) when it is always applied with one
+    factor; the rotate kernel then computes the cropped window only, and `random` is drawn from in the per-sample chain's order."""
 
     NAMES = ["LoadGraphAndFilterByRandomRadiusd", "ScaleIntensityd", "EnsureChannelFirstd", "Resized", "RandFlipd", "RandRotate90d",
              "RandRotated", "AsDiscreted", "CastToTyped"]
 
+    CROP_AT = NAMES.index("RandRotated") + 1         # the one place a RandCropOrPadd entry may stand: between RandRotated and AsDiscreted
+
     @staticmethod
     def applies(aug_config):
-        if [d.get("name") for d in aug_config] != FusedGraphSegBatches.NAMES or not torch.cuda.is_available():
+        names = [d.get("name") for d in aug_config]
+        both = lambda d: list(d.get("keys", [])) == ["image", "label"]
+        at = FusedGraphSegBatches.CROP_AT
+        if len(names) == len(FusedGraphSegBatches.NAMES) + 1 and names[at] == "RandCropOrPadd":
+            # every sample of a mini-batch needs the window size of the others to be stacked (in the reference as well): prob >= 1 and one factor
+            crop = aug_config[at]
+            if not (both(crop) and crop.get("prob", 0.1) >= 1 and crop.get("min_factor", 1) == crop.get("max_factor", 1)):
+                return False
+            aug_config = list(aug_config[:at]) + list(aug_config[at + 1:])
+            names = names[:at] + names[at + 1:]
+        if names != FusedGraphSegBatches.NAMES or not torch.cuda.is_available():
             return False
         load, scale, _, resize, flip, rot90, rot, disc, cast = aug_config
-        both = lambda d: list(d.get("keys", [])) == ["image", "label"]
         size = resize.get("spatial_size", [0, 1])
         return (both(load) and both(scale) and both(resize) and both(flip) and both(rot90) and both(rot) and both(cast)
                 and list(disc.get("keys", [])) == ["label"] and load.get("max_dropout_prob", 0) == 0 and resize.get("mode") == "bilinear"
@@ -124,14 +137,26 @@ class FusedGraphSegBatches:
         from .data_transforms import advance_python_random, load_graph_cached
         out = {k: [it[k] for it in items] for k in items[0] if k.endswith("_path")}
         rendered = {key: self._render(items, i, key) for i, key in enumerate(("image", "label"))}
-        draws = 0                          # random() draws of tree2img.py:62,78 over the mini-batch: per sample one for the dropout probability
-        for it in items:                   # (first key) and one per in-range edge of either key; only their total moves the stream
+        draws = []                         # random() draws of tree2img.py:62,78 per sample: one for the dropout probability (first key) and one
+        for it in items:                   # per in-range edge of either key; only their number moves the stream
+            n = 0
             for i, key in enumerate(("image", "label")):
                 e, _ = load_graph_cached(it[key])
                 lo = float(self.load["min_radius"][i])
-                draws += int(np.count_nonzero((e[:, 6] >= lo) & (e[:, 6] <= 1.0))) + (1 if i == 0 else 0)
-        advance_python_random(draws)
-        mb = self.aug(rendered["image"], rendered["label"])
+                n += int(np.count_nonzero((e[:, 6] >= lo) & (e[:, 6] <= 1.0))) + (1 if i == 0 else 0)
+            draws.append(n)
+        if self.aug.crop is None:
+            advance_python_random(sum(draws))
+            mb = self.aug(rendered["image"], rendered["label"])
+        else:
+            # RandCropOrPadd draws from the same global stream: the per-sample chain interleaves sample by sample (rasteriser draws, crop draws)
+            frame = self.aug.size or list(rendered["image"].shape[1:])
+            windows = []
+            for n in draws:
+                advance_python_random(n)
+                windows.append(self.aug.draw_crop(frame))
+            mb = self.aug(rendered["image"], rendered["label"], windows=windows)
+        self.last_params = mb["params"]    # the mini-batch's random decisions (flip, rot_k, angle, crop offsets), for inspection
         out["image"], out["label"] = mb["image"].to(self.dtype), mb["label"].to(self.dtype)
         return out
 
