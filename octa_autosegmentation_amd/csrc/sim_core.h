@@ -685,14 +685,45 @@ OCTA_HD inline void pyset_add(PySetView &s, int key, unsigned long long hash) {
 //   second (rung 1):  the groups flagged in xf arrive in their TRUE order and are exempt from both conditions; returns 1 at the first violation
 //                     of another group.
 // 0: certified. Also 1 when a table would exceed s_max.
+//
+// heal (opt-in; off: the strict rule above, which -DOCTA_SIM_SET_NOHEAL compiles everywhere): a violation in a generation that WILL be
+// resized (D >= thr) is not flagged but kept PENDING, because such a generation's only downstream effect is the slot order in which its
+// entries are re-inserted. pf (two bytes per group, all zero on entry): the pending groups of this / the previous generation.
+// With them goes one contiguous pending range [u0, u1) of arrival indices: u0 is the first arrival of the earliest group with a pending
+// violation in the generation (everything behind it may sit on other slots in the reference: displaced keys displace others), u1 the
+// resize count thr, or, if the resizing key's group straddles the resize, the index behind that group's last key (u0 is then at most
+// the group's first key). Groups already in X (rung 0) or exempt (rung 1) never become pending; violations in the final generation
+// (D < thr) are flagged at once as in the strict rule. When the NEXT generation (S' slots, resize count thr') has been placed, the range is
+// accepted iff
+//   (a) every key of the range holds its home slot hash & (S' - 1),
+//   (b) no re-inserted entry outside the range visits a slot held by a key of the range on its probe path to its own slot,
+//   (c) the range ends in front of this generation's resizing key: u1 <= thr' - 1 whenever D >= thr'.
+// Accepted: the pending flags are dropped. Refused: every pending group is flagged (rung 0: into X; rung 1 and xf == nullptr: return 1).
+// Violations of the next generation become pending for the one after it in the same way.
+// Why that is exact. Assume the table in front of the range (behind arrival u0 - 1) equals the reference's. The keys outside the range
+// were placed before any key of it, and a set that only grows never moves an entry: they hold the same old slots for every order, so
+// their relative re-insertion order is fixed; the resize happens at a fixed count of distinct keys. Let P be the placement of the
+// re-inserted entries outside the range, taken alone in that order. By (b) no path in P touches a home of the range, by (a) those homes
+// are free in P and pairwise distinct. So at whatever point of the sequence a key of the range is inserted -- re-inserted in any
+// interleaving, or inserted behind the re-insertion (the keys of a straddling group that did not make it into the old table) -- it
+// takes its home, and no other entry's path changes: the table behind the range is P plus the range's keys on their homes, for every
+// order inside the groups and whichever keys of a straddling group came before the resize. (c) keeps a range from depending on a second
+// resize, and the induction over the groups carries on behind the range as in the strict rule.
 OCTA_HD inline int pyset_order_check(const int *dk, const int *dg, const unsigned long long *hashes, int D, int *own, int *ord0, int *ord1,
-                                     int s_max, unsigned char *xf, bool second) {
+                                     int s_max, unsigned char *xf, bool second, bool heal = false, unsigned char *pf = nullptr) {
+#ifdef OCTA_SIM_SET_NOHEAL
+    heal = false;
+#endif
+    if (!pf) heal = false;                                // (pending groups could not be named)
     int S = 8, n_prev = 0, viol = 0;
+    int u0 = 0, u1 = 0;                                   // the pending range of the previous generation (u1 > u0: there is one)
     int *ord = ord0, *ord_next = ord1;
     while (true) {
         const int thr = (3 * (S - 1) + 4) / 5;            // the insertion that makes fill * 5 >= mask * 3 resizes the table
         const int upto = D < thr ? D : thr;
         const unsigned long long mask = (unsigned long long)(S - 1);
+        const bool defer = heal && D >= thr;
+        const int bank = ord == ord0 ? 0 : 1;             // pf[2 g + bank]: group g is pending from this generation; pf[2 g + (bank ^ 1)]: from the previous one
         for (int p = n_prev; p < upto; p++) ord[p] = p;   // behind the re-inserted entries: the arrivals, in order
         for (int e = 0; e < S; e++) own[e] = -1;
         for (int p = 0; p < upto; p++) {
@@ -708,8 +739,11 @@ OCTA_HD inline int pyset_order_check(const int *dk, const int *dg, const unsigne
                     const int q = own[e];
                     if (q < 0) { own[e] = p; placed = true; break; }
                     if (check && q >= n_prev && dg[q] == dg[k]) {                       // (ord[q] = q behind the re-inserted entries)
-                        if (!xf || second) return 1;
-                        xf[dg[k]] = 1; viol++; check = false;
+                        check = false;
+                        if (!defer) {
+                            if (!xf || second) return 1;
+                            xf[dg[k]] = 1; viol++;
+                        } else if (second || !xf || !xf[dg[k]]) pf[2 * dg[k] + bank] = 1;     // (in X on rung 0: flagged already)
                     }
                     e++;
                 } while (probes--);
@@ -718,16 +752,64 @@ OCTA_HD inline int pyset_order_check(const int *dk, const int *dg, const unsigne
                 i = (i * 5 + 1 + perturb) & mask;
             }
         }
-        if (D < thr) return viol;
         if (D > thr && dg[thr - 1] == dg[thr]) {
-            if (!xf) return 1;
-            if (!second) { xf[dg[thr]] = 1; viol++; }
-            else if (!xf[dg[thr]]) return 1;
+            const int g = dg[thr];
+            if (!heal) {
+                if (!xf) return 1;
+                if (!second) { xf[g] = 1; viol++; }
+                else if (!xf[g]) return 1;
+            } else if (!xf || !xf[g]) pf[2 * g + bank] = 1;     // (in X: flagged already on rung 0, exempt on rung 1)
         }
+        if (heal && u1 > u0) {
+            // the verdict on the previous generation's pending range, on the finished table (an entry's walk from its home to its slot
+            // passes exactly the slots it found held when it was placed)
+            bool ok = !(D >= thr && u1 > thr - 1);        // (c)
+            for (int p = 0; p < upto && ok; p++) {
+                const int k = ord[p];
+                const unsigned long long hsh = hashes[dk[k]];
+                unsigned long long perturb = hsh, i = hsh & mask;
+                if (k >= u0 && k < u1) { ok = own[i] == p; continue; }                  // (a)
+                if (p >= n_prev) continue;
+                for (bool at = false; !at && ok;) {                                     // (b)
+                    unsigned long long e = i;
+                    int probes = (i + 9 <= mask) ? 9 : 0;
+                    do {
+                        const int q = own[e];
+                        if (q == p) { at = true; break; }
+                        if (ord[q] >= u0 && ord[q] < u1) { ok = false; break; }
+                        e++;
+                    } while (probes--);
+                    perturb >>= 5;
+                    i = (i * 5 + 1 + perturb) & mask;
+                }
+            }
+            if (!ok && (!xf || second)) return 1;
+            for (int k = u0; k < u1; k++) {
+                unsigned char *f = &pf[2 * dg[k] + (bank ^ 1)];
+                if (*f) {
+                    if (!ok) { xf[dg[k]] = 1; viol++; }
+                    *f = 0;
+                }
+            }
+        }
+        if (D < thr) return viol;
         const int minused = upto > 50000 ? upto * 2 : upto * 4;
         int newS = 8;
         while (newS <= minused) newS <<= 1;
         if (newS > s_max) return 1;
+        u0 = u1 = 0;
+        if (heal) {
+            // the range this generation leaves: from the first key of the earliest pending group to the resize, or to the end of a pending
+            // group that straddles it
+            int f = n_prev;
+            while (f < thr && !pf[2 * dg[f] + bank]) f++;
+            const bool straddle = D > thr && dg[thr - 1] == dg[thr] && pf[2 * dg[thr] + bank];
+            if (f < thr) {
+                while (f > 0 && dg[f - 1] == dg[f]) f--;
+                u0 = f; u1 = thr;
+                while (straddle && u1 < D && dg[u1] == dg[thr]) u1++;
+            }
+        }
         int c = 0;
         for (int e = 0; e < S; e++) if (own[e] >= 0) ord_next[c++] = ord[own[e]];   // re-insertion in the old table's slot order
         { int *t = ord; ord = ord_next; ord_next = t; }
@@ -736,8 +818,8 @@ OCTA_HD inline int pyset_order_check(const int *dk, const int *dg, const unsigne
     }
 }
 OCTA_HD inline bool pyset_order_free(const int *dk, const int *dg, const unsigned long long *hashes, int D, int *own, int *ord0, int *ord1,
-                                     int s_max) {
-    return pyset_order_check(dk, dg, hashes, D, own, ord0, ord1, s_max, nullptr, false) == 0;
+                                     int s_max, bool heal = false, unsigned char *pf = nullptr) {
+    return pyset_order_check(dk, dg, hashes, D, own, ord0, ord1, s_max, nullptr, false, heal, pf) == 0;
 }
 
 // ------------------------------------------------------------------ libstdc++ std::nth_element restated
@@ -3999,11 +4081,21 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
     const double ek = P.eps_k, ek2 = ek * ek;
     long t0 = OCTA_SUBPROF_T0();
     for (int i = b.tid; i < n_oxy; i += b.nth) A.removed[i] = 0;
-    int *ctl = b.coll() + 100;         // [0] hit pairs, [1] / [2] set when the certificate of rung 0 / rung 1 fails (step 5)
+    int *ctl = b.coll() + 100;         // [0] hit pairs, [1] / [2] set when the certificate of rung 0 / rung 1 fails (step 5); [3] first index of the
+                                       // pending range a table generation leaves, [4] its end behind a straddling group, [5] its verdict (set: refused),
+                                       // [6], [7] the pending range the previous generation left
+    constexpr int HEAL_NONE = 0x7fffffff;
     if (b.tid == 0) { ctl[0] = 0; ctl[1] = 0; ctl[2] = 0; }
     // X of the ladder below: one flag per new node (group). The nearest-node list is dead between the arterial growth and the venous assignment.
     unsigned char *xf = reinterpret_cast<unsigned char *>(A.nn);
-    static_assert((size_t)NCAP <= (size_t)OCAP * sizeof(int), "group flags fit the nearest-node list");
+    // behind X: two pending bytes per group for the certificates (this / the previous table generation, pyset_order_check)
+    unsigned char *pf = xf + NCAP;
+    static_assert((size_t)3 * NCAP <= (size_t)OCAP * sizeof(int), "group and pending flags fit the nearest-node list");
+#ifdef OCTA_SIM_SET_NOHEAL
+    constexpr bool HEAL = false;       // the strict certificates (A/B partner)
+#else
+    constexpr bool HEAL = true;
+#endif
     for (int j = b.tid; j < n_new && j < NCAP; j += b.nth) xf[j] = 0;
     b.sync();
     // 1. (new node, sink) hits from a grid over the new nodes: raw pairs node_local << 14 | sink
@@ -4074,7 +4166,8 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
     // The cKDTree order of a node's hits is observed only through the order in which they enter the CPython set `to_add`, and a
     // set's table depends on its insertion order only where keys contend for slots. A sink enters with the first new node that hits
     // it (its group): the order across groups is the node order, known without a tree. Pass 0 inserts each group's sinks in index
-    // order and certifies that no order inside a group could change the table (pyset_order_check); 45 % of the conversions certify.
+    // order and certifies that no order inside a group could change the table (pyset_order_check); 72 % of the conversions certify
+    // (45 % under the strict certificates, -DOCTA_SIM_SET_NOHEAL: without the healing rule described there).
     //
     // The ladder. Rung 0 does not stop at the first violation of its certificate: it flags the GROUP of every violation -- a same-group
     // blocker on a key's way to its slot, or a resizing key that is not the last of its group -- through all table generations. Call the
@@ -4093,6 +4186,10 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
     //     group is in X (true order): the re-insertion then works on a table that is fixed already.
     // The choice of X needs no proof: ANY X is correct as long as the second certificate passes, so rung 0 may go on flagging on a table
     // that was placed in provisional order.
+    // Healing (both rungs; pyset_order_check has the rule and its proof): a violation in a table generation that is resized afterwards
+    // is not flagged at once. It stays pending until the next generation is placed, and is dropped if every key of the pending range
+    // then sits alone on its home slot, off every re-inserted entry's path and in front of the next resize -- the thrown-away
+    // generation's only trace, the re-insertion order, then cannot be observed. Halves the kd builds (138 -> 71 per sample).
     // Every branch on the rung and on a certificate's outcome is block-uniform: the outcomes are read from ctl[] behind a barrier.
     bool set_in_lds = false;
     int rung = 0;                      // 0: provisional order; 1: kd ranks for X's groups; 2: kd ranks for every pair
@@ -4108,6 +4205,8 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
 #endif
     while (true) {
         const int vslot = rung == 1 ? 2 : 1;       // ctl slot of this rung's certificate
+        if (HEAL && rung < 2)                      // (ordered before the certificate by the barriers of the pair sort)
+            for (int j = b.tid; j < 2 * n_new && j < 2 * NCAP; j += b.nth) pf[j] = 0;
         if (rung > 0) {
             // 3. cKDTree order of the O2 list, only as deep as the sinks in `need` need it; pairs get kd ranks. Rung 1: need = the sinks hit by
             //    X's nodes (bit 1 of their removal flag), ranks for X's pairs. Rung 2: need = every removed sink, ranks for every pair.
@@ -4174,6 +4273,7 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
         auto replay = [&](int *own, int *in_key, unsigned long long *in_hash, int *dk, unsigned long long *dh, int *ord0, int *ord1,
                           const int s_max) __attribute__((always_inline)) -> int {
             int n_ins = 0;
+            if (HEAL && b.tid == 0) { ctl[3] = HEAL_NONE; ctl[4] = 0; ctl[5] = 0; ctl[6] = 0; ctl[7] = 0; }   // no pending range (barriers below)
             for (int p0 = 0; p0 < n_pairs; p0 += b.nth) {          // ordered compaction of the insert stream, b.nth pairs per round
                 const int i = p0 + b.tid;
                 int o = -1, take = 0;
@@ -4244,6 +4344,14 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
                     // the certificate (pyset_order_check): every slot a new key passes before its own is held by a re-inserted entry or by a
                     // key of an earlier group; the key that resizes the table is the last of its group. ord[p] = p behind n_prev. Rung 0 flags
                     // the group of every violation and carries on; rung 1 exempts the flagged groups and stops at a violation.
+                    // Healing: in a generation that will be resized a violation stays pending (pf, range start in ctl[3], its end behind a
+                    // straddling group in ctl[4]) for the verdict behind the NEXT generation's placement. No thread writes xf in such a
+                    // generation's pass, so "already in X" is read without a race.
+                    // The range the previous generation left is [ctl[6], ctl[7]) (empty: none). It lives in the collectives area and every
+                    // step reads it again, so that nothing is carried in registers across the passes and the generations (the kernel is at
+                    // its 256 registers); the pending bytes' bank alternates with the ord tables.
+                    const bool defer = HEAL && D >= thr;
+                    const int bank = ord == ord0 ? 0 : 1;
                     for (int p = n_prev + b.tid; p < upto; p += b.nth) {
                         const unsigned g = (unsigned)dk[p] >> IDX_BITS;
                         if (rung == 1 && xf[g]) continue;
@@ -4255,8 +4363,17 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
                             if (q == p) break;
                             // (q == EMPTY is not reached: the slots in front of a key's own are held)
                             if (q == EMPTY || (q >= n_prev && ((unsigned)dk[q] >> IDX_BITS) == g)) {
-                                if (rung == 0) xf[g] = 1;
-                                atomic_or_int(&ctl[vslot], 1);
+                                if (defer) {
+                                    if (rung == 1 || !xf[g]) {
+                                        pf[2 * g + bank] = 1;
+                                        int f = p;
+                                        while (f > 0 && ((unsigned)dk[f - 1] >> IDX_BITS) == g) f--;
+                                        atomic_min_int(&ctl[3], f);
+                                    }
+                                } else {
+                                    if (rung == 0) xf[g] = 1;
+                                    atomic_or_int(&ctl[vslot], 1);
+                                }
                                 break;
                             }
                             if (lin < nlin) { lin++; continue; }
@@ -4267,13 +4384,72 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
                     }
                     if (b.tid == 0 && D > thr && ((unsigned)dk[thr - 1] >> IDX_BITS) == ((unsigned)dk[thr] >> IDX_BITS)) {
                         const unsigned g = (unsigned)dk[thr] >> IDX_BITS;
-                        if (rung == 0) { xf[g] = 1; atomic_or_int(&ctl[vslot], 1); }
+                        if (HEAL) {
+                            if (!xf[g]) {                         // (in X: flagged already on rung 0, exempt on rung 1)
+                                pf[2 * g + bank] = 1;
+                                int f = thr - 1, e = thr + 1;
+                                while (f > 0 && ((unsigned)dk[f - 1] >> IDX_BITS) == g) f--;
+                                while (e < D && ((unsigned)dk[e] >> IDX_BITS) == g) e++;
+                                atomic_min_int(&ctl[3], f);
+                                ctl[4] = e;
+                            }
+                        }
+                        else if (rung == 0) { xf[g] = 1; atomic_or_int(&ctl[vslot], 1); }
                         else if (!xf[g]) atomic_or_int(&ctl[vslot], 1);
+                    }
+                    if (HEAL && OCTA_UNI(ctl[7]) > OCTA_UNI(ctl[6])) {
+                        const int u0 = OCTA_UNI(ctl[6]), u1 = OCTA_UNI(ctl[7]);
+                        // the verdict on the previous generation's pending range [u0, u1), on the finished table (the priorities make a
+                        // walk from an entry's home to its slot pass exactly the slots the sequential placement found held):
+                        // (a) every key of the range on its home slot, (b) no re-inserted entry in front of the range passes a key of it
+                        for (int p = b.tid; p < upto; p += b.nth) {
+                            const int k = ord[p];
+                            const unsigned long long hsh = dh[k];
+                            unsigned long long i = hsh & mask, perturb = hsh;
+                            if (k >= u0 && k < u1) {
+                                if (own[(int)i] != p) atomic_or_int(&ctl[5], 1);
+                            } else if (p < n_prev) {
+                                int lin = 0, nlin = (i + 9 <= mask) ? 9 : 0;
+                                while (true) {
+                                    const int q = own[(int)i + lin];
+                                    if (q == p || q == EMPTY) break;          // (EMPTY is not reached)
+                                    const int kq = ord[q];
+                                    if (kq >= u0 && kq < u1) { atomic_or_int(&ctl[5], 1); break; }
+                                    if (lin < nlin) { lin++; continue; }
+                                    perturb >>= 5;
+                                    i = (i * 5 + 1 + perturb) & mask;
+                                    nlin = (i + 9 <= mask) ? 9 : 0; lin = 0;
+                                }
+                            }
+                        }
                     }
 #ifdef OCTA_SIM_KD_PARTIAL_REFUSE
                     if (b.tid == 0 && rung == 1) atomic_or_int(&ctl[vslot], 1);
 #endif
                     b.sync();
+                    if (HEAL) {
+                        const int nu0 = OCTA_UNI(ctl[3]), nu1 = OCTA_UNI(ctl[4]), u0 = OCTA_UNI(ctl[6]), u1 = OCTA_UNI(ctl[7]);
+                        if (u1 > u0 || nu0 != HEAL_NONE) {        // (uniform)
+                            // (c): the range ends in front of this generation's resizing key. Refused: the pending groups are flagged.
+                            const bool refused = OCTA_UNI(ctl[5]) != 0 || (D >= thr && u1 > thr - 1);
+                            for (int k = u0 + b.tid; k < u1; k += b.nth) {
+                                const unsigned g = (unsigned)dk[k] >> IDX_BITS;
+                                if (pf[2 * g + (bank ^ 1)]) {
+                                    if (refused) {
+                                        if (rung == 0) xf[g] = 1;
+                                        atomic_or_int(&ctl[vslot], 1);
+                                    }
+                                    pf[2 * g + (bank ^ 1)] = 0;
+                                }
+                            }
+                            b.sync();
+                            if (b.tid == 0) {                     // (next read and written behind the next generation's barriers)
+                                ctl[3] = HEAL_NONE; ctl[4] = 0; ctl[5] = 0;
+                                ctl[6] = nu0 != HEAL_NONE ? nu0 : 0;
+                                ctl[7] = nu0 != HEAL_NONE ? (nu1 ? nu1 : thr) : 0;
+                            }
+                        }
+                    }
                     if (rung == 1 && OCTA_UNLIKELY(ctl[vslot])) break;   // (uniform) rung 2 replays the exact order
                 }
                 if (D < thr) break;                               // no resize behind this generation: its table is the set
@@ -4381,8 +4557,13 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
 #endif
         }
 #undef PSP
+        // n_pairs <= PCAP (clamped above): where the HBM-scratch replay exists, one of the two parallel replays has run, and the one-thread
+        // path below is not compiled into the device code at all
+        constexpr bool ONE_THREAD = !HBM_REPLAY;
+#else
+        constexpr bool ONE_THREAD = true;
 #endif
-        if (!set_in_lds && b.tid == 0) {
+        if (ONE_THREAD && !set_in_lds && b.tid == 0) {
             PySetView S;
             S.hash = A.set_hash; S.key = A.set_key; S.err = &sc->err; S.cap = SETCAP;
             pyset_init(S);
@@ -4398,7 +4579,7 @@ OCTA_HD inline void phase_satisfy_art(const Blk &b, const SimArrays &A, const Si
                     if (rung < 2 && S.used != used) { cw[D] = o; cw[OCAP + D] = (int)(pr >> IDX_BITS); D++; }
                 }
             }
-            if (rung < 2 && pyset_order_check(cw, cw + OCAP, A.hashes, D, cw + 4 * OCAP, cw + 2 * OCAP, cw + 3 * OCAP, SETCAP / 2, xf, rung == 1)) ctl[vslot] = 1;
+            if (rung < 2 && pyset_order_check(cw, cw + OCAP, A.hashes, D, cw + 4 * OCAP, cw + 2 * OCAP, cw + 3 * OCAP, SETCAP / 2, xf, rung == 1, HEAL, pf)) ctl[vslot] = 1;
 #ifdef OCTA_SIM_KD_PARTIAL_REFUSE
             if (rung == 1) ctl[vslot] = 1;
 #endif
