@@ -57,14 +57,16 @@ class DiceBCELoss:
         self.dice = DiceLoss(sigmoid=sigmoid)
 
     def __call__(self, y_pred: torch.Tensor, y: torch.Tensor):
+        # The kernels compute Dice per row of [rows][n] with rows = B * C and n = the spatial size, which is the composition below for
+        # tensors with spatial dimensions only (without them the composition's Dice reduces over nothing, or over everything), and the
+        # entry points take at most 65535 rows (one grid row each). Everything else is the composition's.
+        rows = y_pred.shape[0] * y_pred.shape[1] if y_pred.dim() >= 3 else 0
         if (USE_FUSED_LOSS and self.sigmoid and y_pred.is_cuda and y_pred.dtype in (torch.float32, torch.bfloat16)
-                and y_pred.shape == y.shape and (y_pred.dim() < 2 or y_pred.shape[1] == 1)):
-            return _FusedDiceBCE.apply(y_pred, y, self.dice.smooth_nr, self.dice.smooth_dr)   # one channel: per-sample sums
-        if (USE_FUSED_LOSS and self.sigmoid and y_pred.is_cuda and y_pred.dtype in (torch.float32, torch.bfloat16)
-                and y_pred.shape == y.shape and y_pred.dim() >= 3):
+                and y_pred.shape == y.shape and 0 < rows <= 65535 and y_pred.numel() > 0):
+            if y_pred.shape[1] == 1:
+                return _FusedDiceBCE.apply(y_pred, y, self.dice.smooth_nr, self.dice.smooth_dr)   # one channel: per-sample sums
             # several channels: Dice is a mean over (sample, channel), BCE a mean over all elements -> B * C rows of H * W on the
             # contiguous channel-first logits (what the N-channel head writes)
-            rows = y_pred.shape[0] * y_pred.shape[1]
             return _FusedDiceBCE.apply(y_pred.contiguous().view(rows, -1), y.contiguous().view(rows, -1), self.dice.smooth_nr, self.dice.smooth_dr)
         return (self.dice(y_pred, y) + self.bce(y_pred, y)) / 2
 
