@@ -643,6 +643,28 @@ int octa_frangi_hessian(const float *d_in, float *d_hrr, float *d_hrc, float *d_
 int octa_frangi_eigenvalues(const float *d_in, float *d_l1, float *d_l2, float *d_gamma, int b, int h, int w, int radius, const double *weights,
                             float in_scale, int black_ridges, void *d_ws, void *stream);
 
+/* ---- Grey-level area opening / closing and the SkrGAN sketch filter (configs/config_skrgan.yml, reference models/skrgan.py) ----------
+ * Caller-owned device buffers and workspace, no context, as the OOF and Frangi entry points. float32 planes [b][h][w], 1 <= h, w <=
+ * 4096, 1 <= b <= 65535, 4-connectivity, 1 <= area threshold <= 128 and <= h w (an image of fewer pixels is refused, -2).
+ * Every result is the same on every run and an image of a batch equals that image run alone (csrc/morph.hip). */
+
+/* Bytes of workspace the two calls below need for b images of h x w; 0 for an invalid shape. */
+size_t octa_skr_workspace_bytes(int b, int h, int w);
+
+/* d_out = the area opening of d_in: open(f)(p) = max{ v <= f(p) : the 4-connected component of {f >= v} around p has at least
+ * area_threshold pixels }; every output value is one of the input's. closing != 0: 1 - open(1 - d_in) with both subtractions in
+ * float32 (needs d_ws; the opening alone does not). d_out must not be d_in. Inputs are expected free of NaN. */
+int octa_area_opening(const float *d_in, float *d_out, int b, int h, int w, int area_threshold, int closing, void *d_ws, void *stream);
+
+/* The sketch filter per image: m = sqrt(sobel(x, 0)^2 + sobel(x, 1)^2) (scipy.ndimage.sobel, mode 'reflect'), min/max normalised;
+ * g = scipy.ndimage.gaussian_filter(m) by the 1-D weight table `weights` (HOST memory, 2 radius + 1 doubles, offsets -radius ..
+ * radius, symmetric, at most 96 non-zero taps per side; radius < 0: no Gaussian, g = m); o = the opening of g by area_open,
+ * normalised; d_out = the closing of o by area_close, normalised. All float32, bit-identical to numpy / scipy on the host.
+ * d_magnitude, d_filtered, d_opened (each may be null) receive m, g and o. An image with a constant stage (numpy divides 0 by 0)
+ * is NaN everywhere from that stage on. */
+int octa_skr_filter(const float *d_in, float *d_magnitude, float *d_filtered, float *d_opened, float *d_out, int b, int h, int w, int radius,
+                    const double *weights, int area_open, int area_close, void *d_ws, void *stream);
+
 /* ---- N1-N4: space-colonisation vessel-graph simulator --------------------
  * Replaces, for B independent samples advanced in lock-step on the GPU:
  *   vessel_graph_generation/greenhouse.py:57-137 (Greenhouse.develop_forest) with

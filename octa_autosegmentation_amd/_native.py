@@ -151,6 +151,9 @@ SIGNATURES = {
     "octa_frangi_2d": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_float, c_double, c_double, c_int, c_void_p, c_void_p]),
     "octa_frangi_hessian": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]),
     "octa_frangi_eigenvalues": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]),
+    "octa_skr_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "octa_area_opening": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "octa_skr_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "octa_sim_kat_kd_order": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     "octa_sim_kat_kd_order_signflag": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int32, c_void_p]),
     "octa_sim_kat_sample": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, ctypes.c_int64,
