@@ -201,9 +201,9 @@ class BaseModelABC(nn.Module, ModelInterface, ABC):
         self._after_weight_surgery()
 
     def _after_weight_surgery(self):
-        """Weights were written through .data / load_state_dict: packed bf16 copies of the MFMA path are stale."""
-        from . import mfma_conv
-        mfma_conv.invalidate_all_pack_plans(self)
+        """Weights were written through .data / load_state_dict: packed copies of them are stale."""
+        from . import weight_cache
+        weight_cache.invalidate()
 
     # ---- the step ------------------------------------------------------------------------------------------------
     def autocast(self):

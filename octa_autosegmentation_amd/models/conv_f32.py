@@ -17,29 +17,19 @@ import ctypes
 import torch
 
 from .. import _native
+from . import weight_cache
 
-_EPOCH = [0]         # bumped by invalidate_packs(): every packed copy made before is stale
 
-
-def invalidate_packs():
-    """Weights were rewritten through .data / load_state_dict (no version bump): forget every packed copy."""
-    _EPOCH[0] += 1
+def fwd_layout(w, transposed):
+    """The forward weight layout of `octa_conv2d_f32_nchw` (pure torch, any device): input channel outermost, output channel innermost."""
+    if transposed:          # [Cin][Cout][k][k] -> [Cin][k*k][Cout]
+        return w.permute(0, 2, 3, 1).reshape(w.shape[0], w.shape[2] * w.shape[3], w.shape[1]).contiguous()
+    return w.permute(1, 2, 3, 0).reshape(w.shape[1], w.shape[2] * w.shape[3], w.shape[0]).contiguous()      # [Cout][Cin][K][K] -> [Cin][K*K][Cout]
 
 
 def _packed(weight, transposed):
-    """The kernel's weight layout, cached ON the parameter object (epoch, version, storage address, orientation): a cache keyed by
-    id(weight) served a stale copy when a new parameter was given the id and the storage address of a collected one (two DynUNets
-    built one after the other in a test run: logits off by whole units, about one full test run in eight)."""
-    hit = getattr(weight, "_octa_f32_pack", None)
-    if hit is not None and hit[0] == _EPOCH[0] and hit[1] == weight._version and hit[2] == weight.data_ptr() and hit[3] == transposed:
-        return hit[4]
-    w = weight.detach().float()
-    if transposed:          # [Cin][Cout][k][k] -> [Cin][k*k][Cout]
-        p = w.permute(0, 2, 3, 1).reshape(w.shape[0], w.shape[2] * w.shape[3], w.shape[1]).contiguous()
-    else:                   # [Cout][Cin][K][K] -> [Cin][K*K][Cout]
-        p = w.permute(1, 2, 3, 0).reshape(w.shape[1], w.shape[2] * w.shape[3], w.shape[0]).contiguous()
-    weight._octa_f32_pack = (_EPOCH[0], weight._version, weight.data_ptr(), transposed, p)
-    return p
+    """`fwd_layout` of the parameter, cached on it (weight_cache.cached; the orientation is part of the key)."""
+    return weight_cache.cached(weight, "_octa_fwd_f32", transposed, lambda: fwd_layout(weight.detach().float(), transposed))
 
 
 def _launch(x, wp, wp_offset, bias, y, Cout, cout_w, K, stride, pad, Ho, Wo, osc=1, ooy=0, oox=0):
@@ -48,20 +38,31 @@ def _launch(x, wp, wp_offset, bias, y, Cout, cout_w, K, stride, pad, Ho, Wo, osc
                    N, Cin, H, W, Cout, cout_w, K, stride, pad, Ho, Wo, osc, ooy, oox)
 
 
-def supported(conv):
-    """torch.nn.Conv2d / ConvTranspose2d layers this path evaluates (everything DynUNet-S holds)."""
+def _geometry(conv):
+    """(K, stride, pad, transposed) of an ungrouped, undilated layer with square kernel / stride / padding -- a zero-padded Conv2d, or a
+    ConvTranspose2d with kernel == stride in (1, 2), no padding and no bias -- else None."""
     if conv.groups != 1 or tuple(conv.dilation) != (1, 1):
-        return False
+        return None
     k, s, p = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding)
     if k[0] != k[1] or s[0] != s[1] or p[0] != p[1]:
-        return False
+        return None
     if isinstance(conv, torch.nn.ConvTranspose2d):
-        return k == s and k[0] in (1, 2) and p == (0, 0) and tuple(conv.output_padding) == (0, 0) and conv.bias is None
-    if isinstance(conv, torch.nn.Conv2d):
-        # zero padding up to half the kernel: DynUNet's "same" layers, the GAN networks' 3x3 / 7x7 layers behind a reflection pad (padding 0)
-        # and PatchGAN's 4x4 layers with padding 1
-        return (k[0], s[0]) in ((1, 1), (3, 1), (3, 2), (4, 1), (7, 1)) and 0 <= p[0] <= k[0] // 2 and conv.padding_mode == "zeros"
-    return False
+        ok = k == s and k[0] in (1, 2) and p == (0, 0) and tuple(conv.output_padding) == (0, 0) and conv.bias is None
+        return (k[0], s[0], 0, True) if ok else None
+    if isinstance(conv, torch.nn.Conv2d) and conv.padding_mode == "zeros":
+        return (k[0], s[0], p[0], False)
+    return None
+
+
+def supported(conv):
+    """torch.nn.Conv2d / ConvTranspose2d layers this path evaluates (everything DynUNet-S holds)."""
+    geom = _geometry(conv)
+    if geom is None:
+        return False
+    K, s, pad, transposed = geom
+    # zero padding up to half the kernel: DynUNet's "same" layers, the GAN networks' 3x3 / 7x7 layers behind a reflection pad (padding 0)
+    # and PatchGAN's 4x4 layers with padding 1
+    return transposed or ((K, s) in ((1, 1), (3, 1), (3, 2), (4, 1), (7, 1)) and 0 <= pad <= K // 2)
 
 
 def applies(conv, x):
@@ -102,18 +103,8 @@ def forward(conv, x):
 
 def _layer_kind(conv):
     """(K, stride, pad, transposed) of a layer the gradient kernels cover, else None: every layer kind of DynUNet-S."""
-    if conv.groups != 1 or tuple(conv.dilation) != (1, 1):
-        return None
-    k, s, p = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding)
-    if k[0] != k[1] or s[0] != s[1] or p[0] != p[1]:
-        return None
-    if isinstance(conv, torch.nn.ConvTranspose2d):
-        if k == s and k[0] in (1, 2) and p == (0, 0) and tuple(conv.output_padding) == (0, 0) and conv.bias is None:
-            return (k[0], s[0], 0, True)
-        return None
-    if isinstance(conv, torch.nn.Conv2d) and conv.padding_mode == "zeros" and (k[0], s[0], p[0]) in ((1, 1, 0), (3, 1, 1), (3, 2, 1)):
-        return (k[0], s[0], p[0], False)
-    return None
+    geom = _geometry(conv)
+    return geom if geom is not None and (geom[3] or geom[:3] in ((1, 1, 0), (3, 1, 1), (3, 2, 1))) else None
 
 
 def trainable(conv, x):
@@ -153,15 +144,9 @@ def dgrad_layout(w, kind):
 
 
 def _packed_dgrad(weight, kind):
-    """`dgrad_layout` of the parameter, cached on it like `_packed` (epoch, version, storage address, kind) under its own attribute:
-    the forward and the data-gradient orientations do not evict each other; Adam's in-place step bumps the version, so each step
-    repacks once."""
-    hit = getattr(weight, "_octa_f32_dpack", None)
-    if hit is not None and hit[0] == _EPOCH[0] and hit[1] == weight._version and hit[2] == weight.data_ptr() and hit[3] == kind:
-        return hit[4]
-    p = dgrad_layout(weight.detach().float(), kind)
-    weight._octa_f32_dpack = (_EPOCH[0], weight._version, weight.data_ptr(), kind, p)
-    return p
+    """`dgrad_layout` of the parameter, cached on it like `_packed` under its own slot: the forward and the data-gradient orientations
+    do not evict each other; Adam's in-place step bumps the version, so each step repacks once."""
+    return weight_cache.cached(weight, "_octa_dgrad_f32", kind, lambda: dgrad_layout(weight.detach().float(), kind))
 
 
 def dgrad(conv, gy, x_shape):

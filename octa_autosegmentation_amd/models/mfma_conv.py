@@ -1,8 +1,9 @@
 """Host side of the hand-written MFMA convolution (csrc/conv.hip): NHWC bf16 tensors in, NHWC bf16 out.
 
 Layouts: activations [N, H, W, C] contiguous bfloat16; weights "tap-major" [9, Cout, Cin] bfloat16 (tap = 3*r+s).
-`pack_weight` / `pack_weight_dgrad` convert a torch conv weight [Cout, Cin, 3, 3] (models/networks.py, MONAI
-DynUNet naming) into the forward layout and into the layout whose forward pass IS the data gradient.
+`fwd_layout` / `dgrad_layout` convert a torch conv weight [Cout, Cin, K, K] (models/networks.py, MONAI DynUNet naming) into the
+forward layout and into the layout whose forward pass IS the data gradient (pure torch, any device); `pack_weight` /
+`pack_weight_dgrad` / `pack_convt2x2` serve the same bits from the network's WeightPackPlan when the parameter is registered in one.
 """
 import ctypes
 import os
@@ -10,10 +11,22 @@ import os
 import torch
 
 from .. import _native
+from . import weight_cache
 
 
 def _pad32(c):
     return (c + 31) // 32 * 32
+
+
+def _zero_pad(t, dim, size):
+    """t with axis `dim` zero-padded to `size` entries (t itself when it has them already)."""
+    if t.shape[dim] == size:
+        return t
+    shape = list(t.shape)
+    shape[dim] = size
+    out = t.new_zeros(shape)
+    out.narrow(dim, 0, t.shape[dim]).copy_(t)
+    return out
 
 
 def _bf16c(t):
@@ -123,16 +136,14 @@ def _wgrad_acc(x1, x2, dy, grad, accumulate, stride=1, tap_mask=0x1ff):
     _conv3x3_wgrad(x1, dy, x2, into=grad, accumulate=accumulate, stride=stride, tap_mask=tap_mask)
 
 
-USE_PACK_PLAN = True
-
-
 class WeightPackPlan:
     """All KxK convolution weights of a network packed into both kernel layouts by ONE launch per optimiser step
     (csrc/conv.hip octa_pack_conv_weights) instead of ~7 small torch kernels per layer and step. The plan is
-    refreshed when any parameter's version counter (or storage) changed; `pack_weight*` below look parameters up here
-    and fall back to the torch formulation for tensors that are not registered. Optimisers, `load_state_dict` and every
-    in-place op on the parameter move the counter; writes through `parameter.data` do NOT -- call `invalidate()` after those
-    (`networks.init_weights` does)."""
+    refreshed when any parameter's version counter (or storage) changed or the invalidation epoch moved; `pack_weight*` below
+    look parameters up here and fall back to the torch formulation for tensors that are not registered. Optimisers,
+    `load_state_dict` and every in-place op on the parameter move the counter; writes through `parameter.data` do NOT -- call
+    `weight_cache.invalidate()` after those (`networks.init_weights` does). One buffer and one launch for all parameters: the plan
+    keeps the staleness rule of weight_cache.cached() for the whole list instead of a cache slot per parameter."""
 
     def __init__(self, convs, convts=()):
         """convs: float32 parameters [Cout,Cin,K,K]; convts: ConvTranspose2d(2, 2) parameters [Cin,Cout,2,2]."""
@@ -156,7 +167,7 @@ class WeightPackPlan:
 
     def ensure(self):
         ptrs = [w.data_ptr() for w, _ in self.params]
-        versions = [w._version for w, _ in self.params]
+        versions = (weight_cache.epoch(), [w._version for w, _ in self.params])
         if ptrs != self.ptrs:
             # storage moved (.to(), .bfloat16(), memory_format change ...): the packing kernel reads contiguous fp32 [A][B][K][K]
             for w, _ in self.params:
@@ -170,27 +181,12 @@ class WeightPackPlan:
             _native.launch("octa_pack_conv_weights", self.device, self.table, len(self.params), self.buf)
             self.versions = versions
 
-    def invalidate(self):
-        """After writes that bypass the version counter (`.data`)."""
-        self.versions = None
-
-
-def invalidate_all_pack_plans(module):
-    """Every cached WeightPackPlan below `module` repacks on its next use: call after writes that do not move the
-    parameters' version counters (`.data` writes: dist.broadcast(p.data), EMA, checkpoint surgery)."""
-    for m in module.modules():
-        plan = getattr(m, "_octa_pack_plan", None)
-        if plan is not None:
-            plan.invalidate()
-    from . import conv_f32
-    conv_f32.invalidate_packs()
-
 
 def plan_for_module(module):
     """One WeightPackPlan over every MFMA-shaped convolution weight of `module` (3x3 / 4x4 Conv2d, 2x2 ConvTranspose2d),
     built on first use and cached on the module; None when nothing qualifies (CPU, non-float32 master weights)."""
     plan = getattr(module, "_octa_pack_plan", None)
-    if plan is not None or not USE_PACK_PLAN:
+    if plan is not None:
         return plan
     ok = lambda w: w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
     convs = [m.weight for m in module.modules() if isinstance(m, torch.nn.Conv2d) and m.kernel_size in ((3, 3), (4, 4)) and m.groups == 1
@@ -205,8 +201,6 @@ def plan_for_module(module):
 
 
 def _planned(w, kind):
-    if not USE_PACK_PLAN:
-        return None, None
     ent = getattr(w, "_octa_pack", None)
     if ent is None or ent[0].params[ent[1]][0] is not w or ent[0].params[ent[1]][1] != kind:
         return None, None
@@ -229,44 +223,52 @@ def tap_major(wt):
     return wt.reshape(cp // 16, kk, co, 16).permute(1, 2, 0, 3).reshape(kk, co, cp)
 
 
-def pack_weight(w, cin_pad=None):
+# ---- the two kernel layouts of a weight, pure torch (any device; no cache, no plan) ---------------------------------------
+
+def fwd_layout(w, cin_pad=None):
     """[Cout, Cin, K, K] -> [K*K, Cout, CinP] bf16 (CinP = cin_pad or Cin; padded columns zero), stored slice-major (slice_major())."""
-    co, ci, kk = w.shape[0], w.shape[1], w.shape[2] * w.shape[3]
-    cp = ci if cin_pad is None else cin_pad
+    w = _zero_pad(w, 1, w.shape[1] if cin_pad is None else cin_pad)
+    return slice_major(w.permute(2, 3, 0, 1).reshape(w.shape[2] * w.shape[3], w.shape[0], w.shape[1]).to(torch.bfloat16))
+
+
+def dgrad_layout(w, cin_pad=None):
+    """[Cout, Cin, K, K] -> [K*K, CinP, Cout] bf16 with the taps flipped: conv(dy, this) = dL/dx."""
+    w = _zero_pad(w, 1, w.shape[1] if cin_pad is None else cin_pad)
+    return slice_major(w.flip(2, 3).permute(2, 3, 1, 0).reshape(w.shape[2] * w.shape[3], w.shape[1], w.shape[0]).to(torch.bfloat16))
+
+
+def convt2x2_layouts(w):
+    """ConvTranspose2d(2, 2) weight [Cin, Cout, 2, 2] as the 3x3 kernel wc[a][b][r][s] = w[a][b][r-1][s-1] (zero at r = 0 or
+    s = 0), in both layouts: (fwd_layout(wc) [9, Cin, Cout], dgrad_layout(wc) [9, Cout, Cin])."""
+    wc = w.new_zeros((w.shape[0], w.shape[1], 3, 3))
+    wc[:, :, 1:, 1:] = w
+    return fwd_layout(wc), dgrad_layout(wc)
+
+
+# ---- the same layouts of a parameter: from its WeightPackPlan when it is registered in one, else computed ------------------
+
+def pack_weight(w, cin_pad=None):
+    """fwd_layout(w, cin_pad) of a parameter."""
     plan, i = _planned(w, 0)
-    if plan is not None and plan.geom[i][4] == cp:
+    if plan is not None and plan.geom[i][4] == (w.shape[1] if cin_pad is None else cin_pad):
         return plan.fwd[i]
-    if cp != ci:
-        wp = w.new_zeros((co, cp) + tuple(w.shape[2:]))
-        wp[:, :ci] = w
-        w = wp
-    return slice_major(w.permute(2, 3, 0, 1).reshape(kk, co, cp).to(torch.bfloat16))
+    return fwd_layout(w, cin_pad)
 
 
 def pack_weight_dgrad(w, cin_pad=None):
-    """[Cout, Cin, K, K] -> [K*K, CinP, Cout] bf16 with the taps flipped: conv(dy, this) = dL/dx."""
-    co, ci, kk = w.shape[0], w.shape[1], w.shape[2] * w.shape[3]
-    cp = ci if cin_pad is None else cin_pad
+    """dgrad_layout(w, cin_pad) of a parameter."""
     plan, i = _planned(w, 0)
-    if plan is not None and plan.geom[i][4] == cp:
+    if plan is not None and plan.geom[i][4] == (w.shape[1] if cin_pad is None else cin_pad):
         return plan.dg[i]
-    if cp != ci:
-        wp = w.new_zeros((co, cp) + tuple(w.shape[2:]))
-        wp[:, :ci] = w
-        w = wp
-    return slice_major(w.flip(2, 3).permute(2, 3, 1, 0).reshape(kk, cp, co).to(torch.bfloat16))
+    return dgrad_layout(w, cin_pad)
 
 
 def pack_convt2x2(w):
-    """ConvTranspose2d(2, 2) weight [Cin, Cout, 2, 2] as the 3x3 kernel wc[a][b][r][s] = w[a][b][r-1][s-1] (zero at r = 0 or
-    s = 0), in both layouts: (pack_weight(wc) [9, Cin, Cout], pack_weight_dgrad(wc) [9, Cout, Cin])."""
+    """convt2x2_layouts(w) of a parameter."""
     plan, i = _planned(w, 1)
     if plan is not None and plan.geom[i][4] == w.shape[1]:
         return plan.fwd[i], plan.dg[i]
-    wc = w.new_zeros((w.shape[0], w.shape[1], 3, 3))
-    wc[:, :, 1:, 1:] = w
-    return (slice_major(wc.permute(2, 3, 0, 1).reshape(9, w.shape[0], w.shape[1]).to(torch.bfloat16)),
-            slice_major(wc.flip(2, 3).permute(2, 3, 1, 0).reshape(9, w.shape[1], w.shape[0]).to(torch.bfloat16)))
+    return convt2x2_layouts(w)
 
 
 def conv3x3_nhwc(x, wt, stride=1, in_dilation=1, tap_mask=0x1ff, residual=None):
@@ -286,11 +288,11 @@ def conv3x3_nhwc(x, wt, stride=1, in_dilation=1, tap_mask=0x1ff, residual=None):
     return y
 
 
-# The parity-fused kernel for the two layers that double the image (round 5, csrc/conv.hip conv3x3_s2t_kernel). OCTA_S2T=0 keeps the
-# zero-insertion form of rounds 1-4 (the stride-1 kernel on a virtually dilated input: 4 x the multiply-adds).
-USE_S2T = True
-
-
+# The parity-fused kernel for the two layers that double the image (round 5, csrc/conv.hip conv3x3_s2t_kernel): the data gradient of a
+# stride-2 layer and the 2x2 transposed convolution. Rounds 1-4 ran them as conv3x3_nhwc(..., in_dilation=2), the stride-1 kernel on a
+# virtually zero-inserted input (4 x the multiply-adds; _ConvLazy.backward still does). Four scattered launches, one per output parity
+# (scatter=(2, a, b); drivers in tests/test_conv_gpu.py), measured no faster than that form on MI355X, B = 4, 1216^2 U-Net step:
+# 32.6 vs 32.1 ms (register-staged kernels); stride-2 data gradient 22.0 vs 21.8 ms, transposed convolution 22.15 vs 21.8 ms (DMA-staged).
 def conv3x3_s2t_nhwc(x, wt, tap_mask=0x1ff, residual=None):
     """x [N,H,W,Cin] bf16 (the small image), wt [9,Cout,Cin] bf16 as conv3x3_nhwc(..., in_dilation=2) takes it -> [N,2H,2W,Cout] bf16."""
     assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and wt.dtype == torch.bfloat16 and wt.is_contiguous() and wt.shape[2] == x.shape[3]
@@ -352,82 +354,7 @@ def _conv_fwd_stats(x1, x2, wt, stride, want_stats):
     return y, (slots if slots is not None else tiles)
 
 
-# ---- zero-insertion-free stride-2 data gradient / 2x2 transposed convolution: one scattered launch per parity class
-
-# dX[2h+a] receives dY[h + off] * W[r] for (r, off) in: a = 0 -> (1, 0); a = 1 -> (2, 0), (0, +1). The kernel's tap kr reads
-# offset kr - 1, so off 0 <-> kr 1 and off +1 <-> kr 2.
-_PARITY_TAPS = {0: ((1, 1),), 1: ((2, 1), (0, 2))}   # parity -> ((conv tap r, kernel tap kr), ...)
-_parity_tables = {}
-
-
-def _parity_table(device):
-    """src[p][t] = flat conv tap 3r+s feeding kernel tap t of parity class p = 2a+b (or 0 with valid 0), masks[p]."""
-    key = str(device)
-    if key not in _parity_tables:
-        src = torch.zeros((4, 9), dtype=torch.long)
-        valid = torch.zeros((4, 9), dtype=torch.bfloat16)
-        masks = []
-        for a in (0, 1):
-            for b in (0, 1):
-                m = 0
-                for r, kr in _PARITY_TAPS[a]:
-                    for s_, ks in _PARITY_TAPS[b]:
-                        src[2 * a + b, 3 * kr + ks] = 3 * r + s_
-                        valid[2 * a + b, 3 * kr + ks] = 1
-                        m |= 1 << (3 * kr + ks)
-                masks.append(m)
-        _parity_tables[key] = (src.to(device), valid.to(device), masks)
-    return _parity_tables[key]
-
-
-def _fwd3(x, wt, y, mask, a, b):
-    _conv3x3_fwd(x, wt, y, tap_mask=mask, scatter=(2, a, b))
-
-
-def conv3x3_s2_dgrad(dy, weight):
-    """Data gradient of a stride-2, padding-1 3x3 layer (weight [Cout, Cin, 3, 3]): dy [N,Ho,Wo,Cout] -> [N,2Ho,2Wo,Cin].
-    Four scattered launches (one per output parity) over the taps that reach that parity: no inserted zeros."""
-    n, ho, wo, cout = dy.shape
-    cin = weight.shape[1]
-    src, valid, masks = _parity_table(dy.device)
-    w9 = weight.to(torch.bfloat16).permute(2, 3, 1, 0).reshape(9, cin, cout)          # [tap][ci][co]
-    wp = (w9[src] * valid[:, :, None, None]).contiguous()                              # [4][9][ci][co]
-    dx = torch.empty((n, 2 * ho, 2 * wo, cin), dtype=torch.bfloat16, device=dy.device)
-    for p in range(4):
-        _fwd3(dy, slice_major(wp[p]), dx, masks[p], p >> 1, p & 1)
-    return dx
-
-
-def conv_transpose_2x2_fwd(x, weight):
-    """ConvTranspose2d(k = s = 2) forward, weight [Cin, Cout, 2, 2]: per output parity a 1x1 convolution (kernel tap 4)."""
-    n, h, w, cin = x.shape
-    cout = weight.shape[1]
-    wp = x.new_zeros((4, 9, cout, cin))
-    wp[:, 4] = weight.to(torch.bfloat16).permute(2, 3, 1, 0).reshape(4, cout, cin)
-    y = torch.empty((n, 2 * h, 2 * w, cout), dtype=torch.bfloat16, device=x.device)
-    for p in range(4):
-        _fwd3(x, slice_major(wp[p]), y, 1 << 4, p >> 1, p & 1)
-    return y
-
-
-# Measured on MI355X (B=4, 1216^2 U-Net step), twice: with the register-staged kernels (32.6 vs 32.1 ms) and again with the
-# DMA-staged ones (stride-2 data gradient 22.0 vs 21.8 ms, transposed convolution 22.15 vs 21.8 ms in the same session): the
-# four scattered launches are no faster than one launch over the zero-inserted input -- four passes over the input, four
-# weight repacks and 64/128-byte scattered stores cost what the skipped multiplications save. The zero-insertion form stays.
-USE_PARITY_SCATTER = False          # stride-2 data gradient as four parity classes
-USE_PARITY_SCATTER_CONVT = False    # 2x2 transposed convolution forward as four 1x1 parity classes
-
-
 # ---- autograd bindings ---------------------------------------------------------------------------------------------
-
-def _pad_channels(x, mult=32):
-    c = x.shape[-1]
-    if c % mult == 0:
-        return x
-    out = x.new_zeros(x.shape[:-1] + ((c + mult - 1) // mult * mult,))
-    out[..., :c] = x
-    return out
-
 
 # A/B switch (development aid): cleared, the mailbox is never armed and autograd adds the two skip gradients itself.
 USE_SKIP_GRAD_FUSION = True
@@ -455,10 +382,10 @@ class _Conv3x3NHWC(torch.autograd.Function):
         cin = weight.shape[1]
         ctx.mailbox = None
         ctx.set_materialize_grads(False)      # the statistics output is not differentiable: no zero "gradient" of it (a fill launch per layer)
-        if mailbox is not None and USE_SKIP_GRAD_FUSION and x.requires_grad and x.shape[-1] % 32 == 0 and not (int(stride) == 2 and USE_PARITY_SCATTER):
+        if mailbox is not None and USE_SKIP_GRAD_FUSION and x.requires_grad and x.shape[-1] % 32 == 0:
             ctx.mailbox = mailbox
             mailbox.armed = True
-        xp = _pad_channels(x.contiguous())
+        xp = _zero_pad(x.contiguous(), 3, _pad32(x.shape[3]))
         y, part = _conv_fwd_stats(xp, None, pack_weight(weight, xp.shape[-1]), stride, want_stats)
         ctx.save_for_backward(xp, weight)
         ctx.stride, ctx.cin = int(stride), cin
@@ -478,22 +405,12 @@ class _Conv3x3NHWC(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if st == 2:
                 assert xp.shape[1] % 2 == 0 and xp.shape[2] % 2 == 0, "stride-2 layers need even input sizes"
-            # channel-padded input: the GAN trains the generator THROUGH the segmentor's first layer
-            if st == 2 and USE_PARITY_SCATTER:
-                wd = weight
-                if xp.shape[-1] != cin:
-                    wd = weight.new_zeros((weight.shape[0], xp.shape[-1], 3, 3))
-                    wd[:, :cin] = weight
-                dx = conv3x3_s2_dgrad(dy, wd)
-            else:
-                res = None
-                if ctx.mailbox is not None:
-                    res, ctx.mailbox.pending = ctx.mailbox.pending, None       # the decoder's gradient of the same tensor, if posted
-                if st == 2 and USE_S2T:
-                    dx = conv3x3_s2t_nhwc(dy, pack_weight_dgrad(weight, xp.shape[-1]), 0x1ff, res)
-                else:
-                    dx = conv3x3_nhwc(dy, pack_weight_dgrad(weight, xp.shape[-1]), stride=1, in_dilation=st, residual=res)
-            if xp.shape[-1] != cin:
+            res = None
+            if ctx.mailbox is not None:
+                res, ctx.mailbox.pending = ctx.mailbox.pending, None       # the decoder's gradient of the same tensor, if posted
+            wd = pack_weight_dgrad(weight, xp.shape[-1])
+            dx = conv3x3_s2t_nhwc(dy, wd, 0x1ff, res) if st == 2 else conv3x3_nhwc(dy, wd, residual=res)
+            if xp.shape[-1] != cin:         # channel-padded input: the GAN trains the generator THROUGH the segmentor's first layer
                 dx = dx[..., :cin].contiguous()
         elif ctx.mailbox is not None and ctx.mailbox.pending is not None:
             raise RuntimeError("skip gradient posted but the encoder convolution computes no input gradient")
@@ -570,9 +487,6 @@ def conv3x3_reflect(x, weight, want_stats=False):
     return (y, None) if want_stats else y
 
 
-USE_C1_DGRAD = True      # module switch: the one-channel layer's streaming data gradient (round 5)
-
-
 class _Conv3x3C1(torch.autograd.Function):
     """First layer: one input channel. want_stats: also the InstanceNorm statistics of the result in slot form (double
     [STAT_SLOTS][N][Cout][2], accumulated by the kernel's epilogue: the norm needs no statistics pass). The data gradient -- needed when
@@ -621,8 +535,7 @@ class _Conv3x3C1(torch.autograd.Function):
 
 def conv3x3(x, weight, stride=1, want_stats=False, mailbox=None):
     """want_stats: also return the statistics for instance_norm_leaky_relu_nhwc(..., partials=)."""
-    if (x.shape[-1] == 1 and weight.shape[1] == 1 and stride == 1 and weight.shape[0] in (8, 16, 32, 64)
-            and x.shape[2] <= 3840 and (USE_C1_DGRAD or not x.requires_grad)):
+    if x.shape[-1] == 1 and weight.shape[1] == 1 and stride == 1 and weight.shape[0] in (8, 16, 32, 64) and x.shape[2] <= 3840:
         if want_stats == "tiles":                        # the per-tile form belongs to the MFMA kernel: the norm runs its own statistics pass
             return _Conv3x3C1.apply(x, weight, False), None
         return _Conv3x3C1.apply(x, weight, bool(want_stats))          # streaming first-layer kernels
@@ -732,14 +645,8 @@ class _ConvT2x2NHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight):
         x = x.contiguous()
-        if USE_PARITY_SCATTER_CONVT:
-            y = conv_transpose_2x2_fwd(x, weight)
-        else:
-            # the 3x3 form wc has taps r, s in {1, 2}; flipped for the data-gradient form they sit at r, s in {0, 1}
-            if USE_S2T:
-                y = conv3x3_s2t_nhwc(x, pack_convt2x2(weight)[1], 0b000011011)
-            else:
-                y = conv3x3_nhwc(x, pack_convt2x2(weight)[1], stride=1, in_dilation=2, tap_mask=0b000011011)
+        # the 3x3 form wc has taps r, s in {1, 2}; flipped for the data-gradient form they sit at r, s in {0, 1}
+        y = conv3x3_s2t_nhwc(x, pack_convt2x2(weight)[1], 0b000011011)
         ctx.save_for_backward(x, weight)
         return y
 
@@ -763,22 +670,18 @@ class _ConvT2x2NHWC(torch.autograd.Function):
 
 def _t1x1_packs(weight):
     """[9][Cout][Cin] bf16 operands of the tap-masked 3x3 kernel for a ConvTranspose2d(k = 1) weight [Cin, Cout, 1, 1]: forward
-    (tap 4 = W^T) and data gradient (tap 4 = W); the masked taps are never fetched. Cached on the parameter: version counter + storage
-    + the invalidation epoch that invalidate_all_pack_plans() bumps (writes through `.data` -- dist.broadcast(p.data), EMA, checkpoint
-    surgery -- move neither the counter nor the storage)."""
-    from . import conv_f32
-    key = (conv_f32._EPOCH[0], weight._version, weight.data_ptr())
-    c = getattr(weight, "_octa_t1x1", None)
-    if c is None or c[0] != key:
+    (tap 4 = W^T) and data gradient (tap 4 = W); the masked taps are never fetched. Cached on the parameter (weight_cache.cached).
+    They equal fwd_layout / dgrad_layout of the 3x3 weight whose centre tap is W^T; the centre tap is written directly because it needs
+    no flip: that route would add a torch launch per layer to every optimiser step."""
+    def make():
         cin, cout = weight.shape[0], weight.shape[1]
         wm = weight.detach().reshape(cin, cout).to(torch.bfloat16)
         fwd = torch.zeros((9, cout, cin), dtype=torch.bfloat16, device=weight.device)
         dg = torch.zeros((9, cin, cout), dtype=torch.bfloat16, device=weight.device)
         fwd[4] = wm.t()
         dg[4] = wm
-        c = (key, slice_major(fwd), slice_major(dg))
-        weight._octa_t1x1 = c
-    return c[1], c[2]
+        return slice_major(fwd), slice_major(dg)
+    return weight_cache.cached(weight, "_octa_convt1x1", None, make)
 
 
 class _ConvT1x1NHWC(torch.autograd.Function):
@@ -811,17 +714,12 @@ class _ConvT1x1NHWC(torch.autograd.Function):
 
 
 def conv_transpose_kxk_nhwc(x, weight, k):
-    if k == 2 and x.shape[-1] % 32 == 0 and weight.shape[1] % 32 == 0 and USE_MFMA_CONVT:
-        return _ConvT2x2NHWC.apply(x, weight)
-    if k == 1 and x.shape[-1] % 32 == 0 and weight.shape[1] % 32 == 0 and USE_MFMA_CONVT:
-        return _ConvT1x1NHWC.apply(x, weight)
+    if k in (1, 2) and x.shape[-1] % 32 == 0 and weight.shape[1] % 32 == 0:
+        return (_ConvT2x2NHWC if k == 2 else _ConvT1x1NHWC).apply(x, weight)
     from . import networks
     networks._vendor_fallback("DynUNet transposed convolution (NHWC)", f"k = {k}, {x.shape[-1]} -> {weight.shape[1]} channels: GEMM through hipBLASLt "
                               "(the MFMA kernels need k in (1, 2) and channel counts % 32 == 0)")
     return _conv_transpose_kxk_gemm(x, weight, k)
-
-
-USE_MFMA_CONVT = True
 
 
 def _conv_transpose_kxk_gemm(x, weight, k):
@@ -905,11 +803,8 @@ class _InstNormLReLUHead1NHWC(torch.autograd.Function):
                 dhw.view(hw_shape).to(hw_dtype), dhb.to(hw_dtype) if has_hb else None, None)
 
 
-USE_FUSED_NORM_HEAD = True     # module switch (development aid)
-
-
 def norm_lrelu_head1_ok(c, head_weight):
-    return USE_FUSED_NORM_HEAD and head_weight.shape[0] == 1 and head_weight.shape[1] == c and c in (8, 16, 32, 64, 128, 256)
+    return head_weight.shape[0] == 1 and head_weight.shape[1] == c and c in (8, 16, 32, 64, 128, 256)
 
 
 def instance_norm_leaky_relu_head1_nhwc(x, gamma, beta, negative_slope, eps, head_weight, head_bias, partials=None):

@@ -175,9 +175,9 @@ def _trainer_losses(device, arena, x, y, init=None):
     if init is None:                   # the weights are initialised on the device (its own random stream): start from the CPU's
         init = {k: v.clone() for k, v in tr.impl.model.state_dict().items()}
     else:
-        from octa_autosegmentation_amd.models import conv_f32
+        from octa_autosegmentation_amd.models import weight_cache
         tr.impl.model.load_state_dict(init)
-        conv_f32.invalidate_packs()
+        weight_cache.invalidate()
     out = []
     for _ in range(2):
         _, losses = tr.perform_training_step({"image": x.to(device), "label": y.to(device)})

@@ -198,23 +198,84 @@ def test_transposed_conv_2x2(hip_lib_built, cin, cout):
     assert (wm.grad - wr.grad).abs().max().item() <= wr.grad.abs().max().item() * 1e-3 + 1e-5
 
 
+# ---- zero-insertion-free stride-2 data gradient / 2x2 transposed convolution: one scattered launch per parity class. The product runs
+# the parity-fused kernel instead (models/mfma_conv.py conv3x3_s2t_nhwc has the measurements); these drivers keep the forward kernel's
+# scattered store (scatter = (2, a, b)) under test.
+
+# dX[2h+a] receives dY[h + off] * W[r] for (r, off) in: a = 0 -> (1, 0); a = 1 -> (2, 0), (0, +1). The kernel's tap kr reads
+# offset kr - 1, so off 0 <-> kr 1 and off +1 <-> kr 2.
+_PARITY_TAPS = {0: ((1, 1),), 1: ((2, 1), (0, 2))}   # parity -> ((conv tap r, kernel tap kr), ...)
+
+
+def _parity_table(device):
+    """src[p][t] = flat conv tap 3r+s feeding kernel tap t of parity class p = 2a+b (or 0 with valid 0), masks[p]."""
+    import torch
+    src = torch.zeros((4, 9), dtype=torch.long)
+    valid = torch.zeros((4, 9), dtype=torch.bfloat16)
+    masks = []
+    for a in (0, 1):
+        for b in (0, 1):
+            m = 0
+            for r, kr in _PARITY_TAPS[a]:
+                for s_, ks in _PARITY_TAPS[b]:
+                    src[2 * a + b, 3 * kr + ks] = 3 * r + s_
+                    valid[2 * a + b, 3 * kr + ks] = 1
+                    m |= 1 << (3 * kr + ks)
+            masks.append(m)
+    return src.to(device), valid.to(device), masks
+
+
+def _fwd3(x, wt, y, mask, a, b):
+    from octa_autosegmentation_amd.models import mfma_conv
+    mfma_conv._conv3x3_fwd(x, wt, y, tap_mask=mask, scatter=(2, a, b))
+
+
+def conv3x3_s2_dgrad(dy, weight):
+    """Data gradient of a stride-2, padding-1 3x3 layer (weight [Cout, Cin, 3, 3]): dy [N,Ho,Wo,Cout] -> [N,2Ho,2Wo,Cin].
+    Four scattered launches (one per output parity) over the taps that reach that parity: no inserted zeros."""
+    import torch
+    from octa_autosegmentation_amd.models.mfma_conv import slice_major
+    n, ho, wo, cout = dy.shape
+    cin = weight.shape[1]
+    src, valid, masks = _parity_table(dy.device)
+    w9 = weight.to(torch.bfloat16).permute(2, 3, 1, 0).reshape(9, cin, cout)          # [tap][ci][co]
+    wp = (w9[src] * valid[:, :, None, None]).contiguous()                              # [4][9][ci][co]
+    dx = torch.empty((n, 2 * ho, 2 * wo, cin), dtype=torch.bfloat16, device=dy.device)
+    for p in range(4):
+        _fwd3(dy, slice_major(wp[p]), dx, masks[p], p >> 1, p & 1)
+    return dx
+
+
+def conv_transpose_2x2_fwd(x, weight):
+    """ConvTranspose2d(k = s = 2) forward, weight [Cin, Cout, 2, 2]: per output parity a 1x1 convolution (kernel tap 4)."""
+    import torch
+    from octa_autosegmentation_amd.models.mfma_conv import slice_major
+    n, h, w, cin = x.shape
+    cout = weight.shape[1]
+    wp = x.new_zeros((4, 9, cout, cin))
+    wp[:, 4] = weight.to(torch.bfloat16).permute(2, 3, 1, 0).reshape(4, cout, cin)
+    y = torch.empty((n, 2 * h, 2 * w, cout), dtype=torch.bfloat16, device=x.device)
+    for p in range(4):
+        _fwd3(x, slice_major(wp[p]), y, 1 << 4, p >> 1, p & 1)
+    return y
+
+
 def test_parity_scatter_forms(hip_lib_built):
     """The zero-insertion-free forms (one scattered launch per output parity) agree with torch too."""
     import torch
     import torch.nn.functional as F
-    from octa_autosegmentation_amd.models import mfma_conv
     g = torch.Generator(device="cuda").manual_seed(9)
     w = (torch.randn(64, 32, 3, 3, device="cuda", generator=g) / 17.0).to(torch.bfloat16).float()
     x = torch.randn(1, 32, 24, 40, device="cuda", generator=g).to(torch.bfloat16).float().requires_grad_(True)
     y = F.conv2d(x, w, stride=2, padding=1)
     dy = torch.randn(y.shape, device="cuda", generator=g).to(torch.bfloat16)
     y.backward(dy.float())
-    got = mfma_conv.conv3x3_s2_dgrad(dy.permute(0, 2, 3, 1).contiguous(), w)
+    got = conv3x3_s2_dgrad(dy.permute(0, 2, 3, 1).contiguous(), w)
     _check(got, x.grad.permute(0, 2, 3, 1))
     wt = (torch.randn(64, 32, 2, 2, device="cuda", generator=g) / 8.0).to(torch.bfloat16).float()
     xt = torch.randn(2, 10, 18, 64, device="cuda", generator=g).to(torch.bfloat16)
     want = F.conv_transpose2d(xt.float().permute(0, 3, 1, 2), wt, stride=2).permute(0, 2, 3, 1)
-    _check(mfma_conv.conv_transpose_2x2_fwd(xt, wt), want)
+    _check(conv_transpose_2x2_fwd(xt, wt), want)
 
 
 def test_normalise_on_load_equals_materialised(hip_lib_built):
@@ -416,21 +477,18 @@ def test_epilogue_statistics_feed_the_norm(hip_lib_built):
 def test_weight_pack_plan_is_bit_exact_and_follows_updates(hip_lib_built):
     """One-launch packing of all KxK weights (octa_pack_conv_weights) against the torch formulation of the same layouts:
     3x3 with a channel-padded input, 4x4, the 2x2 transposed convolution; bf16 bits identical; refreshed after an in-place
-    optimiser-style update."""
+    optimiser-style update, and after weight_cache.invalidate() where the write went through `.data`."""
     import torch
-    from octa_autosegmentation_amd.models import mfma_conv as mc
+    from octa_autosegmentation_amd.models import mfma_conv as mc, weight_cache
     g = torch.Generator(device="cuda").manual_seed(5)
     mk = lambda *s: torch.nn.Parameter(torch.randn(*s, device="cuda", generator=g))
     w3, w3p, w4, wt = mk(64, 32, 3, 3), mk(32, 1, 3, 3), mk(128, 64, 4, 4), mk(64, 32, 2, 2)
     plan = mc.WeightPackPlan([w3, w3p, w4], [wt])
 
     def ref():
-        mc.USE_PACK_PLAN = False
-        try:
-            return [mc.pack_weight(w3), mc.pack_weight_dgrad(w3), mc.pack_weight(w3p, 32), mc.pack_weight_dgrad(w3p, 32),
-                    mc.pack_weight(w4), mc.pack_weight_dgrad(w4), *mc.pack_convt2x2(wt)]
-        finally:
-            mc.USE_PACK_PLAN = True
+        with torch.no_grad():
+            return [mc.fwd_layout(w3), mc.dgrad_layout(w3), mc.fwd_layout(w3p, 32), mc.dgrad_layout(w3p, 32),
+                    mc.fwd_layout(w4), mc.dgrad_layout(w4), *mc.convt2x2_layouts(wt)]
 
     def got():
         return [mc.pack_weight(w3), mc.pack_weight_dgrad(w3), mc.pack_weight(w3p, 32), mc.pack_weight_dgrad(w3p, 32),
@@ -443,6 +501,15 @@ def test_weight_pack_plan_is_bit_exact_and_follows_updates(hip_lib_built):
     with torch.no_grad():
         for w in (w3, w3p, w4, wt):
             w.add_(0.25)
+    for a, b in zip(got(), ref()):
+        assert torch.equal(a.view(torch.int16), b.view(torch.int16))
+    # a write through `.data` moves neither version counter nor storage: stale, as documented, until the epoch moves
+    before = [t.clone() for t in ref()]
+    for w in (w3, w3p, w4, wt):
+        w.data.mul_(2.0)
+    for a, b, c in zip(got(), before, ref()):
+        assert torch.equal(a.view(torch.int16), b.view(torch.int16)) and not torch.equal(a.view(torch.int16), c.view(torch.int16))
+    weight_cache.invalidate()
     for a, b in zip(got(), ref()):
         assert torch.equal(a.view(torch.int16), b.view(torch.int16))
     # an unregistered tensor takes the torch formulation

@@ -166,19 +166,40 @@ def test_lr_schedulers_attach_like_the_reference_by_default():
 
 def test_t1x1_packs_follow_the_invalidation_epoch():
     """A write through `.data` moves neither the version counter nor the storage: the cached packs of the 1x1 transposed convolution
-    must be rebuilt after invalidate_all_pack_plans() (round-4 advisor item)."""
-    from octa_autosegmentation_amd.models import mfma_conv
+    must be rebuilt after weight_cache.invalidate() (round-4 advisor item)."""
+    from octa_autosegmentation_amd.models import mfma_conv, weight_cache
     w = torch.nn.Parameter(torch.randn(64, 32, 1, 1))
     f0, d0 = mfma_conv._t1x1_packs(w)
     assert mfma_conv._t1x1_packs(w)[0] is f0                         # cached
     w.data.mul_(2.0)
     assert mfma_conv._t1x1_packs(w)[0] is f0                         # nothing moved: stale, as documented
-    holder = torch.nn.Module()
-    holder.w = w
-    mfma_conv.invalidate_all_pack_plans(holder)
+    weight_cache.invalidate()
     f1, d1 = mfma_conv._t1x1_packs(w)
     assert f1 is not f0 and torch.equal(mfma_conv.tap_major(f1)[4].float(), w.detach().reshape(64, 32).t().to(torch.bfloat16).float())
     assert torch.equal(mfma_conv.tap_major(d1)[4].float(), w.detach().reshape(64, 32).to(torch.bfloat16).float())
+
+
+def test_init_weights_invalidates_every_packed_copy():
+    """networks.init_weights writes through `.data` (no version bump, same storage): the fp32 forward and data-gradient packs and the
+    1x1 transposed convolution's bf16 packs taken before it must not be served after it."""
+    from octa_autosegmentation_amd.models import conv_f32, mfma_conv
+    torch.manual_seed(4)
+    conv = torch.nn.Conv2d(4, 8, 3, padding=1, bias=False)
+    convt = torch.nn.ConvTranspose2d(64, 32, 1, bias=False)
+    w, wt, kind = conv.weight, convt.weight, (3, 1, 1, False)
+    old = (conv_f32._packed(w, False).clone(), conv_f32._packed_dgrad(w, kind).clone(), mfma_conv._t1x1_packs(wt))
+    v = (w._version, wt._version)
+    networks.init_weights(conv, 'normal', 0.5)
+    networks.init_weights(convt, 'normal', 0.5)
+    assert (w._version, wt._version) == v                            # the case at hand: nothing but the epoch tells
+    assert not torch.equal(conv_f32._packed(w, False), old[0]) and not torch.equal(conv_f32._packed_dgrad(w, kind), old[1])
+    assert torch.equal(conv_f32._packed(w, False), conv_f32.fwd_layout(w.detach().float(), False))
+    assert torch.equal(conv_f32._packed_dgrad(w, kind), conv_f32.dgrad_layout(w.detach().float(), kind))
+    f1, d1 = mfma_conv._t1x1_packs(wt)
+    assert f1 is not old[2][0] and d1 is not old[2][1]
+    wc = torch.zeros(32, 64, 3, 3)
+    wc[:, :, 1, 1] = wt.detach().reshape(64, 32).t()                 # the 1x1 transposed layer as a 3x3 convolution weight: centre tap W^T
+    assert torch.equal(f1, mfma_conv.fwd_layout(wc)) and torch.equal(d1, mfma_conv.dgrad_layout(wc))
 
 
 def test_noise_transforms_match_the_reference_fixture():
@@ -399,7 +420,7 @@ def test_f32_weight_pack_cache_cannot_serve_a_collected_parameters_copy():
     allocator reuse ids and addresses readily -- and every pack must be the current parameter's."""
     import gc
     import torch
-    from octa_autosegmentation_amd.models import conv_f32
+    from octa_autosegmentation_amd.models import conv_f32, weight_cache
     reused = 0
     seen = set()
     for k in range(40):
@@ -416,7 +437,7 @@ def test_f32_weight_pack_cache_cannot_serve_a_collected_parameters_copy():
             w.add_(1.0)                                        # version bump: repacked
         assert float(conv_f32._packed(w, False).max()) == float(k + 1)
         w.data.fill_(-1.0)                                     # no version bump: callers invalidate
-        conv_f32.invalidate_packs()
+        weight_cache.invalidate()
         assert float(conv_f32._packed(w, False).max()) == -1.0
         del w, p, pt
         gc.collect()

@@ -154,8 +154,8 @@ def _bf16_params(net):
     with torch.no_grad():
         for p in net.parameters():
             p.copy_(p.to(torch.bfloat16).float())
-    from octa_autosegmentation_amd.models import mfma_conv
-    mfma_conv.invalidate_all_pack_plans(net)
+    from octa_autosegmentation_amd.models import weight_cache
+    weight_cache.invalidate()
 
 
 def test_resnet_generator_mfma_path_against_fp32_on_the_same_weights():
