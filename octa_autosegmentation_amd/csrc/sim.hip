@@ -1,22 +1,29 @@
-// sim.hip -- N1-N4: the vessel-graph simulator on gfx950. One 256-thread workgroup advances one
-// sample through the block-cooperative phases of sim_core.h; B samples advance in lock-step with
-// two launches per iteration (the host only serves the rare leaf-bifurcation LAPACK requests in
-// between). No collective, no inter-workgroup communication: samples are independent.
+// sim.hip -- N1-N4: the vessel-graph simulator on gfx950. One 256-thread workgroup advances one sample through the block-cooperative phases
+// of sim_core.h. No collective, no inter-workgroup communication: samples are independent.
 //
-//   launch A(it):  [venous ordered pass + CO2 removal of it-1]  O2 sampling, arterial nearest-node
-//                  assignment (LDS-tiled), dict-order sort (LDS bitonic), per-node speculation
-//   host:          bifurcation requests -> numpy/LAPACK callback -> results
-//   launch B(it):  arterial ordered pass (RNG draws, node creation, Murray with bit-exact glibc pow),
-//                  O2->CO2 conversion (cKDTree order + CPython set order emulated in LDS / by one
-//                  lane), venous assignment + speculation
-//   host:          bifurcation requests
-// Per-sample state stays resident in HBM (about 16 MB per sample, dominated by the pre-generated
-// candidate stream); LDS (155,648 B dynamic) holds tiles, sort keys and the kd key/index arrays.
+// The design is the PERSISTENT form: ONE launch (sim_persistent_kernel, two workgroups per CU) runs every iteration of every sample; a
+// workgroup takes the next sample of the batch from a device counter and comes back for another. Per half-step of an iteration:
+//   [venous | arterial ordered pass of the forest the last mailbox answered (RNG draws, node creation, Murray with bit-exact glibc pow) and
+//   its satisfaction step (O2->CO2 conversion: cKDTree order + CPython set order emulated in LDS / by one lane; CO2 removal)]
+//   [O2 sampling]  nearest-node assignment (LDS-tiled), dict-order sort (LDS bitonic), per-node speculation of the OTHER forest
+//   mailbox: the rare leaf-bifurcation requests (numpy/LAPACK callback) go to the host through pinned memory; only the sample that posted
+//   them waits. A workgroup whose answer does not come within SimKnobs::park_ms PARKS -- records its resume point and leaves the kernel
+//   (mail_roundtrip) --; the host serves parked requests at the kernel boundary and launches again for them.
+// The host side of a run is sim_run_impl: fill_samples (sim_host.h), upload_samples, run_persistent (launch, mailbox service, relaunch; its
+// "no progress for 120 s" bound is the only way a run gives up on a kernel), report_errors.
+//
+// The LOCK-STEP form (OCTA_SIM_LOCKSTEP=1: run_lockstep, sim_iter_a_kernel / sim_iter_b_kernel, two launches per iteration with the host
+// serving requests in between) is the round-1 design, kept as the comparison form: tests/test_sim_gpu.py
+// test_lockstep_and_persistent_forms_agree holds the two to the same bytes.
+//
+// Per-sample state stays resident in HBM (about 16 MB per sample, dominated by the pre-generated candidate stream); LDS (155,648 B dynamic)
+// holds tiles, sort keys and the kd key/index arrays.
 
 #include <chrono>
+#include <memory>
 #include <vector>
 
-#include "common.h"
+#include "sim_ops.h"
 #include "sim_host.h"
 #include <thread>
 #include <atomic>
@@ -26,39 +33,9 @@
 using namespace OCTA_SIMK;
 
 // This file is compiled TWICE (build.py): the default build for the 3 x 3 mm^2 configurations (LDS-resident tables, two samples per
-// CU) and -DOCTA_SIM_LARGE=1 for wide fields of view (sim_core.h). Each build exports its entry points under its own suffix;
-// csrc/sim_api.cpp owns the public octa_sim_* names of include/octa_hip.h and picks the build per simulator (octa_sim_create).
-#if OCTA_SIM_LARGE
-#define OCTA_SIM_T octa_simL_impl
-#define OCTA_SIM_FN(name) octa_simL_##name
-#else
-#define OCTA_SIM_T octa_simS_impl
-#define OCTA_SIM_FN(name) octa_simS_##name
-#endif
-#define octa_sim_create OCTA_SIM_FN(create)
-#define octa_sim_destroy OCTA_SIM_FN(destroy)
-#define octa_sim_run OCTA_SIM_FN(run)
-#define octa_sim_run_states OCTA_SIM_FN(run_states)
-#define octa_sim_np_state OCTA_SIM_FN(np_state)
-#define octa_sim_edge_offsets OCTA_SIM_FN(edge_offsets)
-#define octa_sim_export_edges OCTA_SIM_FN(export_edges)
-#define octa_sim_export_edges_device OCTA_SIM_FN(export_edges_device)
-#define octa_sim_trace OCTA_SIM_FN(trace)
-#define octa_sim_stats OCTA_SIM_FN(stats)
-#define octa_sim_kd_paths OCTA_SIM_FN(kd_paths)
-#define octa_sim_assign_paths OCTA_SIM_FN(assign_paths)
-#define octa_sim_fields OCTA_SIM_FN(fields)
-#define octa_sim_service_stats OCTA_SIM_FN(service_stats)
-#define octa_sim_geometry OCTA_SIM_FN(geometry)
-#define octa_sim_spans OCTA_SIM_FN(spans)
-#define octa_sim_timing OCTA_SIM_FN(timing)
-#define octa_sim_kat_kd_order OCTA_SIM_FN(kat_kd_order)
-#define octa_sim_kat_kd_order_signflag OCTA_SIM_FN(kat_kd_order_signflag)
-#define octa_sim_kat_sample OCTA_SIM_FN(kat_sample)
-struct OCTA_SIM_T;
-extern "C" void octa_sim_destroy(OCTA_SIM_T *S);
-extern "C" long long octa_sim_next_ticket(void);
-extern "C" int *octa_sim_launch_flag(int device);
+// CU) and -DOCTA_SIM_LARGE=1 for wide fields of view (sim_core.h). Everything here has internal linkage; a build exports one symbol, its
+// operations table (csrc/sim_ops.h, at the end of this file). csrc/sim_api.cpp owns the public octa_sim_* names of include/octa_hip.h and
+// binds each simulator to one build's table (octa_sim_create).
 
 namespace {
 
@@ -393,17 +370,17 @@ OCTA_PROBE_KERNEL(probe_kd_build, kd_build(b, A.oxy, A.sc->n_oxy, A.kd_idx, A.kd
 // memory. Samples are no longer in lock step, so a launch lasts as long as its slowest sample's SUM of phases
 // instead of the sum of per-iteration maxima, and there are no per-iteration launches or stream syncs.
 struct HostMail {
-    BifRequest *reqs;    // pinned host [B][REQ_PER_SAMPLE]     device -> host
-    double *results;     // pinned host [B][REQ_PER_SAMPLE][6]  host -> device
-    int *req_n;          // pinned host [B]                     device -> host
-    int *req_ticket;     // pinned host [B]                     device -> host (2*it+1: arterial pass, 2*it+2: venous)
-    int *resp_ticket;    // pinned host [B]                     host -> device
-    int *done;           // pinned host [1]                     device -> host: workgroups that have left the kernel
-    long timeout_ticks;  // device-side bound on one wait for the host (100 MHz wall clock)
-    long park_ticks;     // a workgroup that has waited this long parks (0: never, wait until timeout_ticks as round 1 did)
-    int *launch_flag;    // device [8]: the launches' sign-in block (csrc/sim_api.cpp octa_sim_launch_flag), or NULL
-    int ticket;          // this launch's ticket
-    long *req_time;      // pinned host [B]: device clock at publication (-DOCTA_SIM_PROF_MAIL builds write it, OCTA_SIM_MAIL_DIAG=1 reads it)
+    BifRequest *reqs = nullptr;    // pinned host [B][REQ_PER_SAMPLE]     device -> host
+    double *results = nullptr;     // pinned host [B][REQ_PER_SAMPLE][6]  host -> device
+    int *req_n = nullptr;          // pinned host [B]                     device -> host
+    int *req_ticket = nullptr;     // pinned host [B]                     device -> host (2*it+1: arterial pass, 2*it+2: venous)
+    int *resp_ticket = nullptr;    // pinned host [B]                     host -> device
+    int *done = nullptr;           // pinned host [1]                     device -> host: workgroups that have left the kernel
+    long timeout_ticks = 0;        // device-side bound on one wait for the host (100 MHz wall clock)
+    long park_ticks = 0;           // a workgroup that has waited this long parks (0: never, wait until timeout_ticks as round 1 did)
+    int *launch_flag = nullptr;    // device [8]: the launches' sign-in block (csrc/sim_api.cpp octa_sim_launch_flag), or NULL
+    int ticket = 0;                // this launch's ticket
+    long *req_time = nullptr;      // pinned host [B]: device clock at publication (-DOCTA_SIM_PROF_MAIL builds write it, OCTA_SIM_MAIL_DIAG=1 reads it)
 };
 constexpr int REQ_PER_SAMPLE = OCTA_SIM_LARGE ? 256 : 32;    // bifurcation requests of one sample per mailbox round trip (6.2 KB each, pinned host memory)
 constexpr int ERR_HOST_TIMEOUT = 2048;
@@ -692,99 +669,100 @@ sim_export_kernel(BatchPtrs B, const long *__restrict__ edge_off, int n_trees, d
     }
 }
 
-}  // namespace
+// ---- host side. A HIP handle that its holder releases; not copyable, a vector of them moves.
+template <class H, hipError_t (*Free)(H)>
+struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(Owned &&o) noexcept : h(o.h) { o.h = nullptr; }
+    ~Owned() { reset(); }
+    void reset() { if (h) { hipError_t e = Free(h); (void)e; h = nullptr; } }
+    template <class T> T *as() const { return static_cast<T *>(h); }
+};
+using DevMem = Owned<void *, hipFree>;
+using PinnedMem = Owned<void *, hipHostFree>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
 
-struct OCTA_SIM_T {
+// host-side record of the mailbox service of the last run (octa_sim_service_stats; always kept)
+struct ServiceStats {
+    double max_gap_ms = 0, max_bif_ms = 0;      // longest pass of the service loop, longest bifurcation callback
+    long tickets = 0, relaunches = 0, parked = 0, passes = 0;
+};
+
+struct Sim {
     octa_ctx *ctx = nullptr;
     int B = 0;
+    SimKnobs knobs;                 // the environment as octa_sim_create found it (sim_host.h)
     SimConfig cfg;
     SimConst C;
     std::vector<IterParams> iters;
     BatchPtrs P;
-    std::vector<void *> allocs;
+    std::vector<DevMem> allocs;     // everything dev_alloc handed out: P's arrays and the geometry mask
     std::vector<unsigned short> fixed_valid;   // geometry file: the valid voxels (i, j, k), shared by all samples
-    unsigned char *d_mask = nullptr;           // geometry file: the mask in HBM (SimConst::mask)
-    long *d_edge_off = nullptr;     // [B + 1] row offsets for the device-side edge export
-    BifRequest *h_reqs = nullptr;   // pinned [2*REQ_CAP]
-    double *h_results = nullptr;    // pinned [2*REQ_CAP*6]
-    int *h_req_count = nullptr;     // pinned [2]
-    HostMail mail = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr};  // pinned mailbox of the persistent form
-    bool lockstep = false;          // OCTA_SIM_LOCKSTEP=1: two launches per iteration (the round-1 form)
-    double mail_timeout_ms = 30000; // OCTA_SIM_MAIL_TIMEOUT_MS: device-side bound on one wait for the host when parking is off
-    double park_ms = 100.0;         // OCTA_SIM_PARK_MS: a workgroup that has waited this long for its answer parks (0: never). Normal answers
-                                    // take tens of microseconds; 3 ms (until the end of round 2) also parked workgroups whenever a busy host
-                                    // descheduled the service thread for a few milliseconds, and a park costs a drain + relaunch. Round 6:
-                                    // 20 -> 100 ms. A parked sample is re-run ALONE at the launch's end (+400 ms for a 512-sample launch);
-                                    // one headline run in ~16 lost a launch that way to a host stall of a few tens of milliseconds, which
-                                    // costs its own length when it is waited out. The episodes parking exists for (a launch whose tickets
-                                    // the host stops seeing) take 80 ms longer to resolve.
-    int last_ticket = 0;            // ticket of the last persistent-kernel launch of this simulator
-    int grid_cap = 512;             // workgroups per launch of the persistent kernel (SIM_WG_PER_CU per CU; OCTA_SIM_GRID overrides)
-    int test_stall_ms = 0;          // OCTA_SIM_TEST_HOST_STALL_MS (test hook): the service thread sleeps once with a ticket pending
-    long spin_scans = 4096;         // idle mailbox scans before the service thread starts sleeping 20 us between scans
-    double diag_max_gap_ms = 0, diag_max_bif_ms = 0;
-    long diag_tickets = 0, diag_relaunches = 0, diag_parked = 0, diag_passes = 0;
+    DevMem d_edge_off;              // long [B + 1] row offsets for the device-side edge export
+    PinnedMem h_reqs, h_results, h_req_count;  // lock-step form: BifRequest [2*REQ_CAP], double [2*REQ_CAP*6], int [4]
+    HostMail mail;                  // pinned mailbox of the persistent form: views into the three blocks below
+    PinnedMem mail_reqs, mail_results, mail_words;
+    ServiceStats svc;
     bool ran = false;
-    void *init_stage = nullptr;     // pinned staging of a run's per-sample set-up (valid-voxel lists, generator states)
-    size_t init_stage_bytes = 0;
+    PinnedMem init_stage;           // pinned staging of a run's per-sample set-up (stage_layout: valid-voxel lists, generator states)
     // host copies for export
     std::vector<SampleScalars> h_sc;
     // kernel timing of the last run (HIP events on the launch stream)
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    Event ev[3];
     double ms_a = 0, ms_b = 0, ms_total = 0, ms_host_bif = 0;
     long n_a = 0, n_b = 0, n_bif_req = 0;
     size_t bytes = 0;
     // pinned staging + stream of octa_sim_export_edges
-    void *export_stage = nullptr;
+    PinnedMem export_stage;
     size_t export_cap = 0;
-    hipStream_t export_stream = nullptr;
+    Stream export_stream;
 };
-
-namespace {
+inline Sim *sim_of(void *impl) { return static_cast<Sim *>(impl); }
 
 template <class T>
-int dev_alloc(OCTA_SIM_T *S, T **p, size_t count) {
-    void *q = nullptr;
+int dev_alloc(Sim *S, T **p, size_t count) {
+    DevMem q;
     size_t bytes = count * sizeof(T);
-    // experiment knob (DESIGN.md 4.1 "Open"): OCTA_SIM_ALLOC=finegrained | uncached places the simulator's HBM state in fine-grained /
-    // uncached device memory (other MTYPE: other caching rules of the vector L1 and the L2)
-    static const int alloc_mode = [] { const char *e = getenv("OCTA_SIM_ALLOC"); return !e ? 0 : (!strcmp(e, "finegrained") ? 1 : (!strcmp(e, "uncached") ? 2 : 0)); }();
-    hipError_t e = alloc_mode == 1 ? hipExtMallocWithFlags(&q, bytes ? bytes : 16, hipDeviceMallocFinegrained)
-                 : alloc_mode == 2 ? hipExtMallocWithFlags(&q, bytes ? bytes : 16, hipDeviceMallocUncached)
-                                   : hipMalloc(&q, bytes ? bytes : 16);
+    const int mode = S->knobs.alloc_mode;
+    hipError_t e = mode == 1 ? hipExtMallocWithFlags(&q.h, bytes ? bytes : 16, hipDeviceMallocFinegrained)
+                 : mode == 2 ? hipExtMallocWithFlags(&q.h, bytes ? bytes : 16, hipDeviceMallocUncached)
+                             : hipMalloc(&q.h, bytes ? bytes : 16);
     if (e != hipSuccess) { octa::set_error("octa_sim: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); return -1; }
-    S->allocs.push_back(q);
+    *p = q.as<T>();
+    S->allocs.push_back(std::move(q));
     S->bytes += bytes;
-    *p = reinterpret_cast<T *>(q);
     return 0;
 }
+inline int pinned_alloc(PinnedMem *m, size_t bytes, unsigned flags = hipHostMallocDefault) { return hipHostMalloc(&m->h, bytes, flags) == hipSuccess ? 0 : -1; }
 
-}  // namespace
-
-extern "C" int octa_sim_create(octa_ctx *ctx, const octa_sim_config *c, int B, OCTA_SIM_T **out) {
+// Builds into a unique_ptr: every return before the last line frees what has been allocated so far.
+int sim_create(octa_ctx *ctx, const octa_sim_config *c, int B, void **out) {
     if (!ctx || !c || !out || B <= 0) { octa::set_error("octa_sim_create: bad arguments"); return -2; }
     *out = nullptr;
     if (c->n_modes < 1 || c->n_modes > 8) { octa::set_error("octa_sim_create: n_modes must be 1..8"); return -2; }
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    OCTA_SIM_T *S = new (std::nothrow) OCTA_SIM_T();
+    std::unique_ptr<Sim> S(new (std::nothrow) Sim());
     if (!S) { octa::set_error("octa_sim_create: out of host memory"); return -1; }
     S->ctx = ctx;
     S->B = B;
+    S->knobs = read_knobs(SIM_WG_PER_CU * (ctx->num_cus > 0 ? ctx->num_cus : 256));
     SimConfig &cfg = S->cfg;
     cfg.param_scale = c->param_scale; cfg.d = c->d; cfg.r = c->r; cfg.faz_mean = c->faz_radius_mean; cfg.faz_std = c->faz_radius_std;
     cfg.rotation_radius = c->rotation_radius; cfg.fc0 = c->faz_center[0]; cfg.fc1 = c->faz_center[1];
     cfg.sx = c->size[0]; cfg.sy = c->size[1]; cfg.sz = c->size[2]; cfg.n_trees = c->n_trees;
     int nw = 0;
     for (int w = 0; w < 4; w++) { cfg.walls[w] = c->walls[w]; nw += c->walls[w] ? 1 : 0; }
-    if (c->n_source_walls < 0 || c->n_source_walls > 6) { octa::set_error("octa_sim_create: n_source_walls must be 0..6"); delete S; return -2; }
+    if (c->n_source_walls < 0 || c->n_source_walls > 6) { octa::set_error("octa_sim_create: n_source_walls must be 0..6"); return -2; }
     if (c->n_source_walls > 0) {
         nw = cfg.n_wall_list = c->n_source_walls;
         for (int w = 0; w < nw; w++) {
             cfg.wall_list[w] = c->source_walls[w];
-            if (cfg.wall_list[w] < 0 || cfg.wall_list[w] > 5) { octa::set_error("octa_sim_create: source_walls[%d] = %d is not a wall (0..5)", w, cfg.wall_list[w]); delete S; return -2; }
+            if (cfg.wall_list[w] < 0 || cfg.wall_list[w] > 5) { octa::set_error("octa_sim_create: source_walls[%d] = %d is not a wall (0..5)", w, cfg.wall_list[w]); return -2; }
             if (cfg.wall_list[w] >= 4 && !c->geometry && c->forest_type == 0) {   // simulation_space.py:82-87 reads `self.valid_pixels`, which nothing sets
                 octa::set_error("octa_sim_create: the z source walls need a sampling geometry file (the reference fails without one)");
-                delete S; return -2;
+                return -2;
             }
         }
     }
@@ -793,113 +771,104 @@ extern "C" int octa_sim_create(octa_ctx *ctx, const octa_sim_config *c, int B, O
         const int *g = c->geometry_shape;
         if (g[0] < 1 || g[1] < 1 || g[2] < 1 || g[0] > 65535 || g[1] > 65535 || g[2] > 65535 || (size_t)g[0] * g[1] * g[2] > ((size_t)1 << 26)) {
             octa::set_error("octa_sim_create: sampling geometry [%d][%d][%d]: every dimension must be 1..65535 and the mask at most 2^26 voxels", g[0], g[1], g[2]);
-            delete S; return -2;
+            return -2;
         }
         for (int k = 0; k < 3; k++) cfg.gshape[k] = g[k];
         cfg.geometry.assign(c->geometry, c->geometry + (size_t)g[0] * g[1] * g[2]);
         const double gs = (double)cfg.gs();
         cfg.sx = g[0] / gs; cfg.sy = g[1] / gs; cfg.sz = g[2] / gs;       // shape = geometry.shape / max(geometry.shape)
-        if (cfg.forest_type != 0) { octa::set_error("octa_sim_create: a sampling geometry with nerve forests is not supported"); delete S; return -2; }
+        if (cfg.forest_type != 0) { octa::set_error("octa_sim_create: a sampling geometry with nerve forests is not supported"); return -2; }
         // a wall whose face 0 has no valid voxel: the reference's random.choice raises IndexError on the empty list
         SampleInit probe;
         std::vector<int> face[3];
         init_mask(cfg, 0.0, &probe, face);
-        if (probe.valid.empty()) { octa::set_error("octa_sim_create: the sampling geometry has no valid voxel"); delete S; return -2; }
+        if (probe.valid.empty()) { octa::set_error("octa_sim_create: the sampling geometry has no valid voxel"); return -2; }
         S->fixed_valid = probe.valid;
         for (int w = 0; w < 6; w++) {
             bool used = false;
             if (cfg.n_wall_list > 0) { for (int k = 0; k < cfg.n_wall_list; k++) used |= cfg.wall_list[k] == w; }
             else used = w < 4 && cfg.walls[w];
-            if (used && face[w >> 1].empty()) { octa::set_error("octa_sim_create: source wall %d: face 0 of the sampling geometry along axis %d has no valid voxel", w, w >> 1); delete S; return -2; }
+            if (used && face[w >> 1].empty()) { octa::set_error("octa_sim_create: source wall %d: face 0 of the sampling geometry along axis %d has no valid voxel", w, w >> 1); return -2; }
         }
     }
-    if (cfg.forest_type != 0 && cfg.forest_type != 1) { octa::set_error("octa_sim_create: forest_type must be 0 (stumps) or 1 (nerve)"); delete S; return -2; }
+    if (cfg.forest_type != 0 && cfg.forest_type != 1) { octa::set_error("octa_sim_create: forest_type must be 0 (stumps) or 1 (nerve)"); return -2; }
     for (int m = 0; m < c->n_modes; m++) {
         const double *q = c->modes[m];
         cfg.modes.push_back(ModeCfg{(int)q[0], (int)q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11], q[12]});
-        if ((int)q[1] > NCANDCAP || (int)q[1] < 0) { octa::set_error("octa_sim_create: N=%d exceeds %d", (int)q[1], NCANDCAP); delete S; return -2; }
+        if ((int)q[1] > NCANDCAP || (int)q[1] < 0) { octa::set_error("octa_sim_create: N=%d exceeds %d", (int)q[1], NCANDCAP); return -2; }
     }
-    if ((nw == 0 && cfg.forest_type == 0) || cfg.n_trees < 1 || 2 * cfg.n_trees > NCAP) { octa::set_error("octa_sim_create: bad forest config"); delete S; return -2; }
-    if (std::ceil(cfg.sx * 76) > 76 || std::ceil(cfg.sy * 76) > 76) { octa::set_error("octa_sim_create: simulation space larger than the unit square"); delete S; return -2; }
+    if ((nw == 0 && cfg.forest_type == 0) || cfg.n_trees < 1 || 2 * cfg.n_trees > NCAP) { octa::set_error("octa_sim_create: bad forest config"); return -2; }
+    if (std::ceil(cfg.sx * 76) > 76 || std::ceil(cfg.sy * 76) > 76) { octa::set_error("octa_sim_create: simulation space larger than the unit square"); return -2; }
     S->iters = build_iter_table(cfg, &S->C);
     BatchPtrs &P = S->P;
     memset(&P, 0, sizeof(P));
     P.C = S->C;
     const size_t nb = (size_t)B;
+    Sim *s = S.get();
     int rc = 0;
     for (int f = 0; f < 2 && !rc; f++) {
-        rc |= dev_alloc(S, &P.npos[f], nb * NCAP * 3); rc |= dev_alloc(S, &P.nrad[f], nb * NCAP); rc |= dev_alloc(S, &P.nkap[f], nb * NCAP);
-        rc |= dev_alloc(S, &P.npar[f], nb * NCAP); rc |= dev_alloc(S, &P.nch0[f], nb * NCAP); rc |= dev_alloc(S, &P.nch1[f], nb * NCAP);
-        rc |= dev_alloc(S, &P.nnch[f], nb * NCAP); rc |= dev_alloc(S, &P.nact[f], nb * NCAP);
-        rc |= dev_alloc(S, &P.nn_prev[f], nb * OCAP); rc |= dev_alloc(S, &P.nn_d2[f], nb * OCAP);
+        rc |= dev_alloc(s, &P.npos[f], nb * NCAP * 3); rc |= dev_alloc(s, &P.nrad[f], nb * NCAP); rc |= dev_alloc(s, &P.nkap[f], nb * NCAP);
+        rc |= dev_alloc(s, &P.npar[f], nb * NCAP); rc |= dev_alloc(s, &P.nch0[f], nb * NCAP); rc |= dev_alloc(s, &P.nch1[f], nb * NCAP);
+        rc |= dev_alloc(s, &P.nnch[f], nb * NCAP); rc |= dev_alloc(s, &P.nact[f], nb * NCAP);
+        rc |= dev_alloc(s, &P.nn_prev[f], nb * OCAP); rc |= dev_alloc(s, &P.nn_d2[f], nb * OCAP);
     }
-    rc |= dev_alloc(S, &P.oxy, nb * OCAP * 3); rc |= dev_alloc(S, &P.co2, nb * CCAP * 3);
-    rc |= dev_alloc(S, &P.cand, nb * NCANDCAP * 3); rc |= dev_alloc(S, &P.py_u, nb * PYCAP); rc |= dev_alloc(S, &P.py_state, nb * 625);
-    rc |= dev_alloc(S, &P.nn, nb * OCAP); rc |= dev_alloc(S, &P.act_list, nb * NCAP);
-    rc |= dev_alloc(S, &P.sorted, nb * SORTCAP); rc |= dev_alloc(S, &P.gnode, nb * GCAP); rc |= dev_alloc(S, &P.gstart, nb * GCAP);
-    rc |= dev_alloc(S, &P.gcount, nb * GCAP); rc |= dev_alloc(S, &P.rec, nb * GCAP);
-    rc |= dev_alloc(S, &P.glist, nb * GCAP); rc |= dev_alloc(S, &P.child_group, nb * NCAP); rc |= dev_alloc(S, &P.fl_rec, nb * 2 * MURRAY_FLUSH_LDS);
-    rc |= dev_alloc(S, &P.kd_idx, nb * OCAP); rc |= dev_alloc(S, &P.kd_rank, nb * OCAP);
-    rc |= dev_alloc(S, &P.removed, nb * OCAP); rc |= dev_alloc(S, &P.ven_near, nb * OCAP); rc |= dev_alloc(S, &P.hashes, nb * OCAP);
-    rc |= dev_alloc(S, &P.pairs, nb * PCAP); rc |= dev_alloc(S, &P.set_hash, nb * SETCAP); rc |= dev_alloc(S, &P.set_key, nb * SETCAP);
-    rc |= dev_alloc(S, &P.grid_pts, nb * GRID_N * 3); rc |= dev_alloc(S, &P.cand_idx, nb * NCANDCAP);
-    rc |= dev_alloc(S, &P.tmp_int, nb * (OCAP + 2 * NCANDCAP)); rc |= dev_alloc(S, &P.tmp_dbl, nb * OCAP * 3);
-    rc |= dev_alloc(S, &P.sc, nb); rc |= dev_alloc(S, &P.iters, S->iters.size() + 1);
-    rc |= dev_alloc(S, &P.reqs, (size_t)2 * REQ_CAP); rc |= dev_alloc(S, &P.req_count, 4); rc |= dev_alloc(S, &P.bif_results, (size_t)2 * REQ_CAP * 6);
-    rc |= dev_alloc(S, &P.mt_state, nb * 625); rc |= dev_alloc(S, &P.valid_count, nb);
+    rc |= dev_alloc(s, &P.oxy, nb * OCAP * 3); rc |= dev_alloc(s, &P.co2, nb * CCAP * 3);
+    rc |= dev_alloc(s, &P.cand, nb * NCANDCAP * 3); rc |= dev_alloc(s, &P.py_u, nb * PYCAP); rc |= dev_alloc(s, &P.py_state, nb * 625);
+    rc |= dev_alloc(s, &P.nn, nb * OCAP); rc |= dev_alloc(s, &P.act_list, nb * NCAP);
+    rc |= dev_alloc(s, &P.sorted, nb * SORTCAP); rc |= dev_alloc(s, &P.gnode, nb * GCAP); rc |= dev_alloc(s, &P.gstart, nb * GCAP);
+    rc |= dev_alloc(s, &P.gcount, nb * GCAP); rc |= dev_alloc(s, &P.rec, nb * GCAP);
+    rc |= dev_alloc(s, &P.glist, nb * GCAP); rc |= dev_alloc(s, &P.child_group, nb * NCAP); rc |= dev_alloc(s, &P.fl_rec, nb * 2 * MURRAY_FLUSH_LDS);
+    rc |= dev_alloc(s, &P.kd_idx, nb * OCAP); rc |= dev_alloc(s, &P.kd_rank, nb * OCAP);
+    rc |= dev_alloc(s, &P.removed, nb * OCAP); rc |= dev_alloc(s, &P.ven_near, nb * OCAP); rc |= dev_alloc(s, &P.hashes, nb * OCAP);
+    rc |= dev_alloc(s, &P.pairs, nb * PCAP); rc |= dev_alloc(s, &P.set_hash, nb * SETCAP); rc |= dev_alloc(s, &P.set_key, nb * SETCAP);
+    rc |= dev_alloc(s, &P.grid_pts, nb * GRID_N * 3); rc |= dev_alloc(s, &P.cand_idx, nb * NCANDCAP);
+    rc |= dev_alloc(s, &P.tmp_int, nb * (OCAP + 2 * NCANDCAP)); rc |= dev_alloc(s, &P.tmp_dbl, nb * OCAP * 3);
+    rc |= dev_alloc(s, &P.sc, nb); rc |= dev_alloc(s, &P.iters, S->iters.size() + 1);
+    rc |= dev_alloc(s, &P.reqs, (size_t)2 * REQ_CAP); rc |= dev_alloc(s, &P.req_count, 4); rc |= dev_alloc(s, &P.bif_results, (size_t)2 * REQ_CAP * 6);
+    rc |= dev_alloc(s, &P.mt_state, nb * 625); rc |= dev_alloc(s, &P.valid_count, nb);
     if (cfg.fixed()) {       // one voxel list and the mask itself, shared by every sample
+        unsigned char *d_mask = nullptr;
         P.valid_stride = 0;
-        rc |= dev_alloc(S, &P.valid, S->fixed_valid.size());
-        rc |= dev_alloc(S, &S->d_mask, cfg.geometry.size());
+        rc |= dev_alloc(s, &P.valid, S->fixed_valid.size());
+        rc |= dev_alloc(s, &d_mask, cfg.geometry.size());
         if (!rc) {
             OCTA_HIP_CHECK(hipMemcpy(P.valid, S->fixed_valid.data(), S->fixed_valid.size() * 2, hipMemcpyHostToDevice));
-            OCTA_HIP_CHECK(hipMemcpy(S->d_mask, cfg.geometry.data(), cfg.geometry.size(), hipMemcpyHostToDevice));
-            P.C.mask = S->d_mask;
+            OCTA_HIP_CHECK(hipMemcpy(d_mask, cfg.geometry.data(), cfg.geometry.size(), hipMemcpyHostToDevice));
+            P.C.mask = d_mask;
         }
     } else {
         P.valid_stride = (size_t)76 * 76 * 3;
-        rc |= dev_alloc(S, &P.valid, nb * P.valid_stride);
+        rc |= dev_alloc(s, &P.valid, nb * P.valid_stride);
     }
-    rc |= dev_alloc(S, &P.n_per_iter, S->iters.size() + 1);  // kept for diagnostics
-    rc |= dev_alloc(S, &P.next_sample, 4);
-    rc |= dev_alloc(S, &P.trace, nb * (S->iters.size() + 1) * 4);
+    rc |= dev_alloc(s, &P.n_per_iter, S->iters.size() + 1);  // kept for diagnostics
+    rc |= dev_alloc(s, &P.next_sample, 4);
+    rc |= dev_alloc(s, &P.trace, nb * (S->iters.size() + 1) * 4);
 #ifdef OCTA_SIM_DEBUG_SAT
-    rc |= dev_alloc(S, &P.dbg, nb * (S->iters.size() + 1) * 16);
+    rc |= dev_alloc(s, &P.dbg, nb * (S->iters.size() + 1) * 16);
 #endif
     P.wg_scratch = nullptr;
 #if OCTA_SIM_LARGE
-    rc |= dev_alloc(S, &P.wg_scratch, nb * (size_t)SIM_USER_BYTES);
+    rc |= dev_alloc(s, &P.wg_scratch, nb * (size_t)SIM_USER_BYTES);
 #endif
     P.n_samples = B;
     if (!rc) {       // pinned staging of a run's per-sample set-up (sim_run_impl): allocated here, not in the first run
-        const size_t n_mt = (size_t)B * 625, n_valid = (size_t)B * P.valid_stride;
-        const size_t stage_need = ((n_valid * 2 + 255) & ~(size_t)255) + 2 * n_mt * 4;
-        if (hipHostMalloc(&S->init_stage, stage_need) != hipSuccess) { octa::set_error("octa_sim_create: hipHostMalloc (set-up staging) failed"); S->init_stage = nullptr; rc = -1; }
-        else { S->init_stage_bytes = stage_need; memset(S->init_stage, 0, stage_need); }
+        const size_t stage_need = stage_layout(B, P.valid_stride);
+        if (pinned_alloc(&S->init_stage, stage_need)) { octa::set_error("octa_sim_create: hipHostMalloc (set-up staging) failed"); rc = -1; }
+        else memset(S->init_stage.h, 0, stage_need);
     }
-    if (!rc) {
-        hipError_t e1 = hipHostMalloc((void **)&S->h_reqs, sizeof(BifRequest) * 2 * REQ_CAP);
-        hipError_t e2 = hipHostMalloc((void **)&S->h_results, sizeof(double) * 2 * REQ_CAP * 6);
-        hipError_t e3 = hipHostMalloc((void **)&S->h_req_count, sizeof(int) * 4);
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { octa::set_error("octa_sim_create: hipHostMalloc failed"); rc = -1; }
-    }
+    if (!rc && (pinned_alloc(&S->h_reqs, sizeof(BifRequest) * 2 * REQ_CAP) | pinned_alloc(&S->h_results, sizeof(double) * 2 * REQ_CAP * 6) |
+                pinned_alloc(&S->h_req_count, sizeof(int) * 4))) { octa::set_error("octa_sim_create: hipHostMalloc failed"); rc = -1; }
     if (!rc) {
         const unsigned fl = hipHostMallocCoherent | hipHostMallocMapped;
-        hipError_t e1 = hipHostMalloc((void **)&S->mail.reqs, sizeof(BifRequest) * nb * REQ_PER_SAMPLE, fl);
-        hipError_t e2 = hipHostMalloc((void **)&S->mail.results, sizeof(double) * nb * REQ_PER_SAMPLE * 6, fl);
-        hipError_t e3 = hipHostMalloc((void **)&S->mail.req_n, sizeof(int) * (nb * 5 + 18), fl);      // + [B] longs: publication stamps of the diagnostic build
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { octa::set_error("octa_sim_create: hipHostMalloc (mailbox) failed"); rc = -1; }
-        else { S->mail.req_ticket = S->mail.req_n + nb; S->mail.resp_ticket = S->mail.req_n + 2 * nb; S->mail.done = S->mail.req_n + 3 * nb; S->mail.req_time = reinterpret_cast<long *>(S->mail.req_n + ((3 * nb + 16 + 1) & ~(size_t)1)); }
-        const char *ls = getenv("OCTA_SIM_LOCKSTEP");
-        S->lockstep = ls && ls[0] == '1';
-        if (const char *e = getenv("OCTA_SIM_MAIL_TIMEOUT_MS")) { double v = atof(e); if (v >= 1.0) S->mail_timeout_ms = v; }
-        if (const char *e = getenv("OCTA_SIM_TEST_HOST_STALL_MS")) S->test_stall_ms = atoi(e);
-        if (const char *e = getenv("OCTA_SIM_PARK_MS")) { double v = atof(e); if (v >= 0.0) S->park_ms = v; }
-        S->grid_cap = SIM_WG_PER_CU * (ctx->num_cus > 0 ? ctx->num_cus : 256);
-        if (const char *e = getenv("OCTA_SIM_GRID")) { int v = atoi(e); if (v >= 1) S->grid_cap = v; }
-        // several ranks per host (one service thread per step in flight and rank): give the cores back sooner
-        if (const char *e = getenv("WORLD_SIZE")) { if (atoi(e) > 1) S->spin_scans = 256; }
-        if (const char *e = getenv("OCTA_SIM_SPIN_SCANS")) S->spin_scans = atol(e);
+        HostMail &M = S->mail;
+        if (pinned_alloc(&S->mail_reqs, sizeof(BifRequest) * nb * REQ_PER_SAMPLE, fl) | pinned_alloc(&S->mail_results, sizeof(double) * nb * REQ_PER_SAMPLE * 6, fl) |
+            pinned_alloc(&S->mail_words, sizeof(int) * (nb * 5 + 18), fl)) {      // + [B] longs: publication stamps of the diagnostic build
+            octa::set_error("octa_sim_create: hipHostMalloc (mailbox) failed"); rc = -1;
+        } else {
+            M.reqs = S->mail_reqs.as<BifRequest>(); M.results = S->mail_results.as<double>(); M.req_n = S->mail_words.as<int>();
+            M.req_ticket = M.req_n + nb; M.resp_ticket = M.req_n + 2 * nb; M.done = M.req_n + 3 * nb;
+            M.req_time = reinterpret_cast<long *>(M.req_n + ((3 * nb + 16 + 1) & ~(size_t)1));
+        }
     }
     if (!rc) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sim_persistent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS);
@@ -910,60 +879,33 @@ extern "C" int octa_sim_create(octa_ctx *ctx, const octa_sim_config *c, int B, O
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(sim_iter_b_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS);
         if (e != hipSuccess) { octa::set_error("octa_sim_create: cannot reserve %zu B of LDS: %s", SIM_LDS, hipGetErrorString(e)); rc = -1; }
     }
-    if (!rc) for (int k = 0; k < 3; k++) if (hipEventCreate(&S->ev[k]) != hipSuccess) { octa::set_error("octa_sim_create: hipEventCreate failed"); rc = -1; }
-    if (rc) { octa_sim_destroy(S); return -1; }
-    *out = S;
+    if (!rc) for (int k = 0; k < 3; k++) if (hipEventCreate(&S->ev[k].h) != hipSuccess) { octa::set_error("octa_sim_create: hipEventCreate failed"); rc = -1; }
+    if (rc) return -1;
+    *out = S.release();
     return 0;
 }
 
-extern "C" void octa_sim_destroy(OCTA_SIM_T *S) {
+void sim_destroy(void *impl) {
+    Sim *S = sim_of(impl);
     if (!S) return;
     hipError_t e = hipSetDevice(S->ctx->device);
-    for (void *p : S->allocs) e = hipFree(p);
-    if (S->h_reqs) e = hipHostFree(S->h_reqs);
-    if (S->h_results) e = hipHostFree(S->h_results);
-    if (S->h_req_count) e = hipHostFree(S->h_req_count);
-    if (S->mail.reqs) e = hipHostFree(S->mail.reqs);
-    if (S->mail.results) e = hipHostFree(S->mail.results);
-    if (S->mail.req_n) e = hipHostFree(S->mail.req_n);
-    for (int k = 0; k < 3; k++) if (S->ev[k]) e = hipEventDestroy(S->ev[k]);
-    if (S->export_stage) e = hipHostFree(S->export_stage);
-    if (S->init_stage) e = hipHostFree(S->init_stage);
-    if (S->export_stream) e = hipStreamDestroy(S->export_stream);
-    if (S->d_edge_off) e = hipFree(S->d_edge_off);
     (void)e;
     delete S;
 }
 
-namespace {
-// what differs between the entry points: how sample s gets its FAZ radius, stump nodes and generator states
-struct SampleSource {
-    const uint32_t *np_seeds = nullptr;
-    const uint64_t *py_seeds = nullptr;
-    const double *faz = nullptr, *stumps = nullptr;        // [B], [B][2][2 * n_trees][3]
-    const uint32_t *np_states = nullptr, *py_states = nullptr;   // [B][625] each: 624 words + position
-    void fill(const SimConfig &cfg, int s, SampleInit *I) const {
-        if (np_seeds) { init_sample(cfg, np_seeds[s], py_seeds[s], I); return; }
-        Mt19937 np, py;
-        memcpy(np.mt, np_states + (size_t)s * 625, 624 * 4); np.idx = (int)np_states[(size_t)s * 625 + 624];
-        memcpy(py.mt, py_states + (size_t)s * 625, 624 * 4); py.idx = (int)py_states[(size_t)s * 625 + 624];
-        const size_t n = (size_t)2 * cfg.n_trees * 3;
-        init_sample_given(cfg, faz[s], stumps + (size_t)s * 2 * n, stumps + (size_t)s * 2 * n + n, np, py, I);
-    }
-};
-int sim_run_impl(OCTA_SIM_T *S, const SampleSource &src, octa_bif_fn bif, void *user, void *stream_);
-}  // namespace
+int sim_run_impl(Sim *S, const SampleSource &src, octa_bif_fn bif, void *user, void *stream_);
 
-extern "C" int octa_sim_run(OCTA_SIM_T *S, const uint32_t *h_np_seeds, const uint64_t *h_py_seeds, octa_bif_fn bif, void *user,
-                            void *stream_) {
+int sim_run(void *impl, const uint32_t *h_np_seeds, const uint64_t *h_py_seeds, octa_bif_fn bif, void *user, void *stream_) {
+    Sim *S = sim_of(impl);
     if (!S || !h_np_seeds || !h_py_seeds || !bif) { octa::set_error("octa_sim_run: bad arguments"); return -2; }
     SampleSource src;
     src.np_seeds = h_np_seeds; src.py_seeds = h_py_seeds;
     return sim_run_impl(S, src, bif, user, stream_);
 }
 
-extern "C" int octa_sim_run_states(OCTA_SIM_T *S, const double *h_faz_radius, const double *h_stumps, const uint32_t *h_np_states,
-                                   const uint32_t *h_py_states, octa_bif_fn bif, void *user, void *stream_) {
+int sim_run_states(void *impl, const double *h_faz_radius, const double *h_stumps, const uint32_t *h_np_states, const uint32_t *h_py_states,
+                   octa_bif_fn bif, void *user, void *stream_) {
+    Sim *S = sim_of(impl);
     if (!S || !h_faz_radius || !h_stumps || !h_np_states || !h_py_states || !bif) { octa::set_error("octa_sim_run_states: bad arguments"); return -2; }
     for (int s = 0; s < S->B; s++)
         if (h_np_states[(size_t)s * 625 + 624] > 624 || h_py_states[(size_t)s * 625 + 624] > 624) { octa::set_error("octa_sim_run_states: corrupt generator state"); return -2; }
@@ -973,322 +915,300 @@ extern "C" int octa_sim_run_states(OCTA_SIM_T *S, const double *h_faz_radius, co
 }
 
 // numpy's generator of sample `sample` after the run: 624 words + position (the candidate stream is its only consumer)
-extern "C" int octa_sim_np_state(OCTA_SIM_T *S, int sample, uint32_t *h_state625) {
+int sim_np_state(void *impl, int sample, uint32_t *h_state625) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_state625 || sample < 0 || sample >= S->B) { octa::set_error("octa_sim_np_state: bad arguments"); return -2; }
     OCTA_HIP_CHECK(hipSetDevice(S->ctx->device));
     OCTA_HIP_CHECK(hipMemcpy(h_state625, S->P.mt_state + (size_t)sample * 625, 625 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
-namespace {
-int sim_run_impl(OCTA_SIM_T *S, const SampleSource &src, octa_bif_fn bif, void *user, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    OCTA_HIP_CHECK(hipSetDevice(S->ctx->device));
+// ---- a run, in stages (sim_run_impl below)
+using clk = std::chrono::steady_clock;
+inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
+
+// Where fill_samples (sim_host.h) leaves a batch's set-up: the voxel lists and generator states in the simulator's pinned block, the small
+// arrays in pageable vectors that live until upload_samples has waited for their copies.
+struct SetupStage {
+    std::vector<SampleScalars> sc;
+    std::vector<unsigned> vcount;
+    std::vector<double> stumps;
+    SampleStaging st;
+    explicit SetupStage(Sim *S) : sc(S->B), vcount(S->B), stumps((size_t)S->B * 2 * 2 * S->cfg.n_trees * 3) {
+        stage_layout(S->B, S->P.valid_stride, S->init_stage.h, &st);
+        st.sc = sc.data(); st.valid_count = vcount.data(); st.stumps = stumps.data();
+    }
+};
+
+// Everything a run's kernels need before the first launch, on `stream` in this order: the per-sample scalars, generator states and voxel
+// lists that fill_samples staged, the CPython uniforms (py_uniform_kernel draws them on the device from the staged state), the iteration
+// table, and the stump nodes of both forests (one strided copy per node array). Returns when every copy out of host memory has completed.
+int upload_samples(Sim *S, const SetupStage &h, hipStream_t stream) {
     const int B = S->B;
     BatchPtrs &P = S->P;
-    const SimConst &C = S->C;
-    // ---- host init of every sample (FAZ radius, validity mask, stumps, RNG streams)
-    {
-        std::vector<SampleScalars> sc(B);
-        // the large staging arrays (18 MB of valid-voxel lists, 2.6 MB of generator states for 512 samples) live in ONE pinned block that a
-        // simulator keeps: allocated and zero-filled per run they cost ~3 ms of page faults and a pageable copy, between two kernels
-        const size_t n_mt = (size_t)B * 625, n_valid = (size_t)B * P.valid_stride;
-        const size_t stage_need = ((n_valid * 2 + 255) & ~(size_t)255) + 2 * n_mt * 4;
-        if (S->init_stage_bytes < stage_need) {
-            if (S->init_stage) OCTA_HIP_CHECK(hipHostFree(S->init_stage));
-            S->init_stage = nullptr; S->init_stage_bytes = 0;
-            OCTA_HIP_CHECK(hipHostMalloc(&S->init_stage, stage_need));
-            S->init_stage_bytes = stage_need;
-            memset(S->init_stage, 0, stage_need);
-        }
-        unsigned short *valid = static_cast<unsigned short *>(S->init_stage);       // entries behind a sample's count are never read
-        unsigned *mt = reinterpret_cast<unsigned *>(static_cast<char *>(S->init_stage) + ((n_valid * 2 + 255) & ~(size_t)255));
-        unsigned *py_mt = mt + n_mt;
-        std::vector<unsigned> vcount(B);
-        const int n0 = 2 * S->cfg.n_trees;
-        std::vector<double> npos((size_t)B * 2 * n0 * 3);
-        constexpr bool time_init = false;      // development aid: host-init timing on stderr
-        const auto t_init0 = std::chrono::steady_clock::now();
-        // the samples are independent: a few host threads share them (round 5: 5.6 of the 6.9 ms this block takes for 512 samples were this
-        // loop on one core, and the block sits between two persistent kernels of the pipeline). OCTA_SIM_INIT_THREADS overrides.
-        static const int init_threads = [] {
-            if (const char *e = getenv("OCTA_SIM_INIT_THREADS")) { const int v = atoi(e); if (v >= 1) return v < 64 ? v : 64; }
-            int world = 1;
-            if (const char *e = getenv("WORLD_SIZE")) { const int v = atoi(e); if (v > 1) world = v; }
-            const int hw = (int)std::thread::hardware_concurrency();
-            const int v = hw / (2 * world);                 // half of this rank's share of the host: the service threads and the trainer need the rest
-            return v < 1 ? 1 : (v > 8 ? 8 : v);
-        }();
-        std::atomic<int> bad_sample{-1};
-        auto fill_range = [&](int s_begin, int s_end) {
-            SampleInit I;
-            I.want_py_u = false;             // the uniforms are drawn on the device from the generator state (py_uniform_kernel)
-            for (int s = s_begin; s < s_end; s++) {
-                src.fill(S->cfg, s, &I);
-                memset(&sc[s], 0, sizeof(SampleScalars));
-                sc[s].faz_radius = I.faz_radius;
-                sc[s].py_cap = PYCAP;
-                sc[s].n_nodes[0] = sc[s].n_nodes[1] = n0;
-                memcpy(&mt[(size_t)s * 625], I.np_state.mt, 624 * 4);
-                mt[(size_t)s * 625 + 624] = (unsigned)I.np_state.idx;
-                vcount[s] = (unsigned)(I.valid.size() / 3);
-                if (vcount[s] == 0) { int none = -1; bad_sample.compare_exchange_strong(none, s); continue; }
-                if (P.valid_stride) memcpy(&valid[(size_t)s * P.valid_stride], I.valid.data(), I.valid.size() * 2);
-                memcpy(&py_mt[(size_t)s * 625], I.py_state.mt, 624 * 4);
-                py_mt[(size_t)s * 625 + 624] = (unsigned)I.py_state.idx;
-                for (int f = 0; f < 2; f++) memcpy(&npos[((size_t)s * 2 + f) * n0 * 3], I.pos[f].data(), sizeof(double) * n0 * 3);
-            }
-        };
-        {
-            const int nt = B >= 64 ? (init_threads < B / 32 ? init_threads : B / 32) : 1;
-            std::vector<std::thread> pool;
-            const int per = (B + nt - 1) / nt;
-            for (int t = 1; t < nt; t++) pool.emplace_back(fill_range, t * per < B ? t * per : B, (t + 1) * per < B ? (t + 1) * per : B);
-            fill_range(0, per < B ? per : B);
-            for (auto &th : pool) th.join();
-        }
-        if (bad_sample.load() >= 0) { octa::set_error("octa_sim_run: sample %d has no valid voxel", bad_sample.load()); return -2; }
-        if (time_init) fprintf(stderr, "[octa_sim] host init: per-sample fill %.2f ms for %d samples\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_init0).count(), B);
-        OCTA_HIP_CHECK(hipMemcpyAsync(P.sc, sc.data(), sizeof(SampleScalars) * B, hipMemcpyHostToDevice, stream));
-        OCTA_HIP_CHECK(hipMemcpyAsync(P.mt_state, mt, n_mt * 4, hipMemcpyHostToDevice, stream));
-        if (P.valid_stride) OCTA_HIP_CHECK(hipMemcpyAsync(P.valid, valid, n_valid * 2, hipMemcpyHostToDevice, stream));
-        OCTA_HIP_CHECK(hipMemcpyAsync(P.valid_count, vcount.data(), vcount.size() * 4, hipMemcpyHostToDevice, stream));
-        OCTA_HIP_CHECK(hipMemcpyAsync(P.py_state, py_mt, n_mt * 4, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(py_uniform_kernel, dim3((unsigned)B), dim3(64), 0, stream, P.py_state, P.py_u, PYCAP);
-        OCTA_HIP_CHECK(hipGetLastError());
-        OCTA_HIP_CHECK(hipMemcpyAsync(P.iters, S->iters.data(), sizeof(IterParams) * S->iters.size(), hipMemcpyHostToDevice, stream));
-        std::vector<int> Ns(S->iters.size() + 1, 0);
-        for (size_t i = 0; i < S->iters.size(); i++) Ns[i] = S->iters[i].N;
-        OCTA_HIP_CHECK(hipMemcpyAsync(P.n_per_iter, Ns.data(), sizeof(int) * Ns.size(), hipMemcpyHostToDevice, stream));
-        // stump nodes: root (kappa 4, no parent) + one child per tree; one strided copy per array puts the
-        // n0 leading entries of every sample's slice in place
-        std::vector<double> rad((size_t)B * n0, C.r), kap((size_t)B * n0, 4.0);
-        std::vector<int> par((size_t)B * n0), c0((size_t)B * n0), c1((size_t)B * n0, -1);
-        std::vector<unsigned char> nch((size_t)B * n0), act((size_t)B * n0, 1);
-        for (size_t k = 0; k < (size_t)B * n0; k++) {
-            const int i = (int)(k % n0);
-            par[k] = (i & 1) ? i - 1 : -1; c0[k] = (i & 1) ? -1 : i + 1; nch[k] = (i & 1) ? 0 : 1;
-        }
-        std::vector<double> pos_f((size_t)B * n0 * 3);
-        auto put = [&](void *dst, size_t elem, const void *src, size_t per_sample_cap, size_t count) -> hipError_t {
-            return hipMemcpy2DAsync(dst, per_sample_cap * elem, src, count * elem, count * elem, (size_t)B, hipMemcpyHostToDevice, stream);
-        };
-        for (int f = 0; f < 2; f++) {
-            OCTA_HIP_CHECK(hipMemsetAsync(P.nact[f], 0, (size_t)B * NCAP, stream));
-            for (int s = 0; s < B; s++) memcpy(&pos_f[(size_t)s * n0 * 3], &npos[((size_t)s * 2 + f) * n0 * 3], sizeof(double) * n0 * 3);
-            OCTA_HIP_CHECK(put(P.npos[f], sizeof(double), pos_f.data(), (size_t)NCAP * 3, (size_t)n0 * 3));
-            OCTA_HIP_CHECK(hipStreamSynchronize(stream));  // pos_f is reused for the second forest
-            OCTA_HIP_CHECK(put(P.nrad[f], sizeof(double), rad.data(), NCAP, n0));
-            OCTA_HIP_CHECK(put(P.nkap[f], sizeof(double), kap.data(), NCAP, n0));
-            OCTA_HIP_CHECK(put(P.npar[f], sizeof(int), par.data(), NCAP, n0));
-            OCTA_HIP_CHECK(put(P.nch0[f], sizeof(int), c0.data(), NCAP, n0));
-            OCTA_HIP_CHECK(put(P.nch1[f], sizeof(int), c1.data(), NCAP, n0));
-            OCTA_HIP_CHECK(put(P.nnch[f], 1, nch.data(), NCAP, n0));
-            OCTA_HIP_CHECK(put(P.nact[f], 1, act.data(), NCAP, n0));
-        }
-        OCTA_HIP_CHECK(hipMemsetAsync(P.req_count, 0, sizeof(int) * 4, stream));
-#ifdef OCTA_SIM_DEBUG_SAT
-        OCTA_HIP_CHECK(hipMemsetAsync(P.dbg, 0xff, sizeof(int) * (size_t)B * (S->iters.size() + 1) * 16, stream));
-#endif
-        OCTA_HIP_CHECK(hipMemsetAsync(P.child_group, 0, sizeof(int) * (size_t)B * NCAP, stream));
-        OCTA_HIP_CHECK(hipStreamSynchronize(stream));  // host vectors go out of scope
-        if (time_init) fprintf(stderr, "[octa_sim] host init: %.2f ms in all (fill + copies + fills)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_init0).count());
+    const size_t n_mt = (size_t)B * 625, n_valid = (size_t)B * P.valid_stride;
+    const int n0 = 2 * S->cfg.n_trees;
+    OCTA_HIP_CHECK(hipMemcpyAsync(P.sc, h.sc.data(), sizeof(SampleScalars) * B, hipMemcpyHostToDevice, stream));
+    OCTA_HIP_CHECK(hipMemcpyAsync(P.mt_state, h.st.np_state, n_mt * 4, hipMemcpyHostToDevice, stream));
+    if (P.valid_stride) OCTA_HIP_CHECK(hipMemcpyAsync(P.valid, h.st.valid, n_valid * 2, hipMemcpyHostToDevice, stream));
+    OCTA_HIP_CHECK(hipMemcpyAsync(P.valid_count, h.vcount.data(), h.vcount.size() * 4, hipMemcpyHostToDevice, stream));
+    OCTA_HIP_CHECK(hipMemcpyAsync(P.py_state, h.st.py_state, n_mt * 4, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(py_uniform_kernel, dim3((unsigned)B), dim3(64), 0, stream, P.py_state, P.py_u, PYCAP);
+    OCTA_HIP_CHECK(hipGetLastError());
+    OCTA_HIP_CHECK(hipMemcpyAsync(P.iters, S->iters.data(), sizeof(IterParams) * S->iters.size(), hipMemcpyHostToDevice, stream));
+    std::vector<int> Ns(S->iters.size() + 1, 0);
+    for (size_t i = 0; i < S->iters.size(); i++) Ns[i] = S->iters[i].N;
+    OCTA_HIP_CHECK(hipMemcpyAsync(P.n_per_iter, Ns.data(), sizeof(int) * Ns.size(), hipMemcpyHostToDevice, stream));
+    // stump nodes: root (kappa 4, no parent) + one child per tree; one strided copy per array puts the
+    // n0 leading entries of every sample's slice in place
+    std::vector<double> rad((size_t)B * n0, S->C.r), kap((size_t)B * n0, 4.0);
+    std::vector<int> par((size_t)B * n0), c0((size_t)B * n0), c1((size_t)B * n0, -1);
+    std::vector<unsigned char> nch((size_t)B * n0), act((size_t)B * n0, 1);
+    for (size_t k = 0; k < (size_t)B * n0; k++) {
+        const int i = (int)(k % n0);
+        par[k] = (i & 1) ? i - 1 : -1; c0[k] = (i & 1) ? -1 : i + 1; nch[k] = (i & 1) ? 0 : 1;
     }
-    // ---- iterations
-    auto serve = [&](int slot) -> int {
-        OCTA_HIP_CHECK(hipMemcpyAsync(S->h_req_count, P.req_count, sizeof(int) * 2, hipMemcpyDeviceToHost, stream));
+    std::vector<double> pos_f((size_t)B * n0 * 3);
+    auto put = [&](void *dst, size_t elem, const void *src, size_t per_sample_cap, size_t count) -> hipError_t {
+        return hipMemcpy2DAsync(dst, per_sample_cap * elem, src, count * elem, count * elem, (size_t)B, hipMemcpyHostToDevice, stream);
+    };
+    for (int f = 0; f < 2; f++) {
+        OCTA_HIP_CHECK(hipMemsetAsync(P.nact[f], 0, (size_t)B * NCAP, stream));
+        for (int s = 0; s < B; s++) memcpy(&pos_f[(size_t)s * n0 * 3], &h.stumps[((size_t)s * 2 + f) * n0 * 3], sizeof(double) * n0 * 3);
+        OCTA_HIP_CHECK(put(P.npos[f], sizeof(double), pos_f.data(), (size_t)NCAP * 3, (size_t)n0 * 3));
+        OCTA_HIP_CHECK(hipStreamSynchronize(stream));  // pos_f is reused for the second forest
+        OCTA_HIP_CHECK(put(P.nrad[f], sizeof(double), rad.data(), NCAP, n0));
+        OCTA_HIP_CHECK(put(P.nkap[f], sizeof(double), kap.data(), NCAP, n0));
+        OCTA_HIP_CHECK(put(P.npar[f], sizeof(int), par.data(), NCAP, n0));
+        OCTA_HIP_CHECK(put(P.nch0[f], sizeof(int), c0.data(), NCAP, n0));
+        OCTA_HIP_CHECK(put(P.nch1[f], sizeof(int), c1.data(), NCAP, n0));
+        OCTA_HIP_CHECK(put(P.nnch[f], 1, nch.data(), NCAP, n0));
+        OCTA_HIP_CHECK(put(P.nact[f], 1, act.data(), NCAP, n0));
+    }
+    OCTA_HIP_CHECK(hipMemsetAsync(P.req_count, 0, sizeof(int) * 4, stream));
+#ifdef OCTA_SIM_DEBUG_SAT
+    OCTA_HIP_CHECK(hipMemsetAsync(P.dbg, 0xff, sizeof(int) * (size_t)B * (S->iters.size() + 1) * 16, stream));
+#endif
+    OCTA_HIP_CHECK(hipMemsetAsync(P.child_group, 0, sizeof(int) * (size_t)B * NCAP, stream));
+    OCTA_HIP_CHECK(hipStreamSynchronize(stream));  // host vectors go out of scope
+    return 0;
+}
+
+// OCTA_SIM_MAIL_DIAG=1 (tools/sim_mailbox_profile.py): what a ticket waits for, from the host's side -- passes of the service loop, and, with
+// a -DOCTA_SIM_PROF_MAIL library, the device's publication stamp against the host's clock. Off, each note is one predictable branch.
+struct MailDiag {
+    const bool on;
+    const clk::time_point wall0;
+    double min_d = 1e300, sum_serv = 0;
+    std::vector<double> lat;
+    long pass_hist[6] = {0, 0, 0, 0, 0, 0};
+    void note_pass(double it_ms) {
+        if (on) pass_hist[it_ms < 0.01 ? 0 : it_ms < 0.03 ? 1 : it_ms < 0.1 ? 2 : it_ms < 0.3 ? 3 : it_ms < 1.0 ? 4 : 5]++;
+    }
+    // host clock at sighting / answer against the device's publication stamp (clock offset = the smallest difference seen)
+    void note_ticket(clk::time_point h_seen, const long *req_time) {
+        if (!on) return;
+        const double d = std::chrono::duration<double, std::micro>(h_seen - wall0).count() - (double)__atomic_load_n(req_time, __ATOMIC_RELAXED) * 1e-2;
+        if (d < min_d) min_d = d;
+        sum_serv += std::chrono::duration<double, std::micro>(clk::now() - h_seen).count();
+        lat.push_back(d);
+    }
+    void print(const Sim *S, double ms_kernels) const {
+        if (!on) return;
+        const ServiceStats &v = S->svc;
+        fprintf(stderr, "[octa] mailbox service: %ld passes over %d tickets in %.1f ms of kernel (%.2f us per pass; <10 us %ld, <30 %ld, <100 %ld, <300 %ld, <1000 %ld, longer %ld; longest %.3f ms), "
+                        "%ld tickets, %.1f ms in the callback\n", v.passes, S->B, ms_kernels, 1e3 * ms_kernels / (double)(v.passes ? v.passes : 1),
+                pass_hist[0], pass_hist[1], pass_hist[2], pass_hist[3], pass_hist[4], pass_hist[5], v.max_gap_ms, v.tickets, S->ms_host_bif);
+        if (!lat.empty() && S->mail.req_time[0] != 0) {
+            long h[7] = {0, 0, 0, 0, 0, 0, 0};
+            double sum = 0;
+            for (double d : lat) { const double x = d - min_d; sum += x; h[x < 10 ? 0 : x < 30 ? 1 : x < 100 ? 2 : x < 300 ? 3 : x < 1000 ? 4 : x < 3000 ? 5 : 6]++; }
+            fprintf(stderr, "[octa]   publication (device clock) -> seen by the host, above the fastest ticket: %.1f us on average (<10 us %ld, <30 %ld, <100 %ld, <300 %ld, <1000 %ld, <3000 %ld, "
+                            "longer %ld); seen -> answered %.1f us\n", sum / (double)lat.size(), h[0], h[1], h[2], h[3], h[4], h[5], h[6], sum_serv / (double)lat.size());
+        }
+    }
+};
+
+// The persistent form: ONE launch runs every iteration of every sample; this thread answers mailbox tickets until all workgroups have
+// signed off (a counter in the pinned block, incremented by the kernel with a system-scope atomic) or the launch has completed. Workgroups
+// whose answer did not reach them in time have PARKED (mail_roundtrip): their requests are served here, at the kernel boundary, and the
+// kernel is launched again for them. While a launch runs this thread's only job is the mailbox; it asks the runtime about the launch only
+// after a millisecond of silence, and gives up on a launch that shows no progress for 120 s.
+__attribute__((noinline, aligned(64))) int run_persistent(Sim *S, octa_bif_fn bif, void *user, hipStream_t stream, clk::time_point wall0) {
+    const int B = S->B;
+    BatchPtrs &P = S->P;
+    HostMail &M = S->mail;
+    const SimKnobs &K = S->knobs;
+    M.timeout_ticks = (long)(K.mail_timeout_ms * 1e5);
+    M.park_ticks = (long)(K.park_ms * 1e5);
+    S->svc = ServiceStats();
+    S->h_sc.resize(B);
+    bool stalled_once = false;
+    double ms_kernels = 0;
+    MailDiag diag{K.mail_diag, wall0};
+    int launches = 0;
+    auto answer = [&](int s, int n) {
+        if (n > REQ_PER_SAMPLE) n = REQ_PER_SAMPLE;
+        if (n <= 0) return;
+        auto t0 = clk::now();
+        bif(n, reinterpret_cast<const octa_bif_request *>(M.reqs + (size_t)s * REQ_PER_SAMPLE), M.results + (size_t)s * REQ_PER_SAMPLE * 6, user);
+        const double bms = ms_since(t0);
+        S->ms_host_bif += bms;
+        if (bms > S->svc.max_bif_ms) S->svc.max_bif_ms = bms;
+        S->n_bif_req += n;
+    };
+    while (true) {
+        for (int s = 0; s < 3 * B + 1; s++) M.req_n[s] = 0;
+        memset(M.req_time, 0, sizeof(long) * (size_t)B);
+        std::vector<int> seen(B, 0);
+        const int *const req_ticket = M.req_ticket;     // a local: the scan below is the loop this thread lives in
+        OCTA_HIP_CHECK(hipMemsetAsync(P.next_sample, 0, sizeof(int), stream));
+        // this launch's ticket and its sign-in counter (csrc/sim_api.cpp): the counter of the launch before the previous one is reused
+        M.launch_flag = octa_sim_launch_flag(S->ctx->device);
+        M.ticket = (int)(octa_sim_next_ticket() & 0x3fffffff);
+        if (M.launch_flag) {
+            OCTA_HIP_CHECK(hipMemsetAsync(M.launch_flag + 1 + (M.ticket & 1), 0, sizeof(int), stream));
+            OCTA_HIP_CHECK(hipMemsetAsync(M.launch_flag + 3 + (M.ticket & 1), 0, sizeof(int), stream));
+        }
+        OCTA_HIP_CHECK(hipEventRecord(S->ev[0].h, stream));
+        const int grid = B < K.grid_cap ? B : K.grid_cap;
+        hipLaunchKernelGGL(sim_persistent_kernel, dim3((unsigned)grid), dim3(SIM_THREADS), SIM_LDS, stream, P, M);
+        OCTA_HIP_CHECK(hipGetLastError());
+        OCTA_HIP_CHECK(hipEventRecord(S->ev[1].h, stream));
+        launches++;
+        long idle = 0;
+        auto last_progress = clk::now(), iter_start = last_progress;
+        int last_done = 0;
+        while (true) {
+            {   // longest single pass of this loop, whatever it was spent in (callback, descheduling, ...)
+                const auto t = clk::now();
+                const double it_ms = std::chrono::duration<double, std::milli>(t - iter_start).count();
+                if (it_ms > S->svc.max_gap_ms) S->svc.max_gap_ms = it_ms;
+                diag.note_pass(it_ms);
+                iter_start = t;
+            }
+            // scan: every sample's request ticket; answer the new ones
+            bool any = false;
+            S->svc.passes++;
+            for (int s = 0; s < B; s++) {
+                const int t = __atomic_load_n(req_ticket + s, __ATOMIC_ACQUIRE);
+                if (t == seen[s]) continue;
+                any = true;
+                if (K.test_stall_ms > 0 && !stalled_once) {   // test hook: the host goes away once, with a ticket pending
+                    stalled_once = true;
+                    std::this_thread::sleep_for(std::chrono::milliseconds(K.test_stall_ms));
+                }
+                const auto h_seen = clk::now();
+                answer(s, __atomic_load_n(M.req_n + s, __ATOMIC_RELAXED));
+                __atomic_store_n(M.resp_ticket + s, t, __ATOMIC_RELEASE);
+                diag.note_ticket(h_seen, M.req_time + s);
+                seen[s] = t;
+                S->svc.tickets++;
+            }
+            // progress check
+            const int done = __atomic_load_n(M.done, __ATOMIC_ACQUIRE);
+            if (done >= B) break;
+            if (any || done != last_done) { idle = 0; last_done = done; last_progress = clk::now(); continue; }
+            if ((++idle & 63) == 0) {
+                const double silent = ms_since(last_progress);
+                if (silent > 1.0) {
+                    hipError_t q = hipEventQuery(S->ev[1].h);
+                    if (q == hipSuccess) break;                       // launch over although not every sign-off was seen
+                    if (q != hipErrorNotReady) { octa::set_error("octa_sim_run: kernel failed: %s", hipGetErrorString(q)); return -1; }
+                    if (silent > 1000.0 * 120.0) { octa::set_error("octa_sim_run: the simulation kernel made no progress for 120 s"); return -1; }
+                }
+                if (idle > K.spin_scans) std::this_thread::sleep_for(std::chrono::microseconds(20));
+            }
+        }
+        float ms = 0;
+        OCTA_HIP_CHECK(hipEventSynchronize(S->ev[1].h));
+        OCTA_HIP_CHECK(hipEventElapsedTime(&ms, S->ev[0].h, S->ev[1].h));
+        ms_kernels += ms;
+        // kernel boundary: everything the launch wrote is visible now
+        OCTA_HIP_CHECK(hipMemcpyAsync(S->h_sc.data(), P.sc, sizeof(SampleScalars) * B, hipMemcpyDeviceToHost, stream));
         OCTA_HIP_CHECK(hipStreamSynchronize(stream));
-        int n = S->h_req_count[slot];
+        int n_parked = 0;
+        for (int s = 0; s < B; s++) {
+            if (!S->h_sc[s].parked || S->h_sc[s].err) continue;
+            n_parked++;
+            answer(s, M.req_n[s]);
+        }
+        if (n_parked == 0) break;
+        S->svc.relaunches++;
+        S->svc.parked += n_parked;
+        if (launches > 4 * (int)S->iters.size() + 16) { octa::set_error("octa_sim_run: %d launches without finishing (parking loop)", launches); return -1; }
+    }
+    S->ms_b = (float)ms_kernels; S->n_b = launches;
+    diag.print(S, ms_kernels);
+    return 0;
+}
+
+// The lock-step form (OCTA_SIM_LOCKSTEP=1): every sample advances one iteration per pair of launches, and between two launches the host
+// serves all bifurcation requests of the batch (`serve`: counts and records come down, the callback's answers go up). Ends with the
+// samples' scalars on the host, where the persistent form has them from its last kernel boundary.
+int run_lockstep(Sim *S, octa_bif_fn bif, void *user, hipStream_t stream) {
+    const int B = S->B;
+    BatchPtrs &P = S->P;
+    BifRequest *h_reqs = S->h_reqs.as<BifRequest>();
+    double *h_results = S->h_results.as<double>();
+    int *h_req_count = S->h_req_count.as<int>();
+    auto serve = [&](int slot) -> int {
+        OCTA_HIP_CHECK(hipMemcpyAsync(h_req_count, P.req_count, sizeof(int) * 2, hipMemcpyDeviceToHost, stream));
+        OCTA_HIP_CHECK(hipStreamSynchronize(stream));
+        int n = h_req_count[slot];
         if (n > REQ_CAP) n = REQ_CAP;
         if (n > 0) {
-            OCTA_HIP_CHECK(hipMemcpyAsync(S->h_reqs, P.reqs + (size_t)slot * REQ_CAP, sizeof(BifRequest) * n, hipMemcpyDeviceToHost, stream));
+            OCTA_HIP_CHECK(hipMemcpyAsync(h_reqs, P.reqs + (size_t)slot * REQ_CAP, sizeof(BifRequest) * n, hipMemcpyDeviceToHost, stream));
             OCTA_HIP_CHECK(hipStreamSynchronize(stream));
-            auto t0 = std::chrono::steady_clock::now();
-            bif(n, reinterpret_cast<const octa_bif_request *>(S->h_reqs), S->h_results, user);
-            S->ms_host_bif += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            auto t0 = clk::now();
+            bif(n, reinterpret_cast<const octa_bif_request *>(h_reqs), h_results, user);
+            S->ms_host_bif += ms_since(t0);
             S->n_bif_req += n;
-            OCTA_HIP_CHECK(hipMemcpyAsync(P.bif_results, S->h_results, sizeof(double) * 6 * n, hipMemcpyHostToDevice, stream));
+            OCTA_HIP_CHECK(hipMemcpyAsync(P.bif_results, h_results, sizeof(double) * 6 * n, hipMemcpyHostToDevice, stream));
             OCTA_HIP_CHECK(hipMemsetAsync(P.req_count + slot, 0, sizeof(int), stream));
         }
         return 0;
     };
-    S->ms_a = S->ms_b = S->ms_total = S->ms_host_bif = 0; S->n_a = S->n_b = S->n_bif_req = 0;
-    auto wall0 = std::chrono::steady_clock::now();
-    if (!S->lockstep) {
-        // ---- persistent form: ONE launch runs every iteration of every sample; this thread answers mailbox tickets until all
-        // workgroups have signed off (a counter in the pinned block, incremented by the kernel with a system-scope atomic) or the
-        // launch has completed. Workgroups whose answer did not reach them in time have PARKED (mail_roundtrip): their requests
-        // are served here, at the kernel boundary, and the kernel is launched again for them. While a launch runs this thread's
-        // only job is the mailbox; it asks the runtime about the launch only after a millisecond of silence.
-        HostMail &M = S->mail;
-        using clk = std::chrono::steady_clock;
-        M.timeout_ticks = (long)(S->mail_timeout_ms * 1e5);
-        M.park_ticks = (long)(S->park_ms * 1e5);
-        S->diag_max_gap_ms = 0; S->diag_tickets = 0; S->diag_max_bif_ms = 0; S->diag_relaunches = 0; S->diag_parked = 0; S->diag_passes = 0;
-        S->h_sc.resize(B);
-        bool stalled_once = false;
-        double ms_kernels = 0;
-        // OCTA_SIM_MAIL_DIAG=1 (tools/sim_mailbox_profile.py): what a ticket waits for, from the host's side -- passes of this loop, and, with a
-        // -DOCTA_SIM_PROF_MAIL library, the device's publication stamp against the host's clock
-        const bool mail_diag = getenv("OCTA_SIM_MAIL_DIAG") != nullptr;
-        double diag_min_d = 1e300, diag_sum_serv = 0;
-        std::vector<double> diag_lat;
-        long pass_hist[6] = {0, 0, 0, 0, 0, 0};
-        int launches = 0;
-        auto answer = [&](int s, int n) {
-            if (n > REQ_PER_SAMPLE) n = REQ_PER_SAMPLE;
-            if (n <= 0) return;
-            auto t0 = clk::now();
-            bif(n, reinterpret_cast<const octa_bif_request *>(M.reqs + (size_t)s * REQ_PER_SAMPLE), M.results + (size_t)s * REQ_PER_SAMPLE * 6, user);
-            const double bms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-            S->ms_host_bif += bms;
-            if (bms > S->diag_max_bif_ms) S->diag_max_bif_ms = bms;
-            S->n_bif_req += n;
-        };
-        while (true) {
-            for (int s = 0; s < 3 * B + 1; s++) M.req_n[s] = 0;
-            memset(M.req_time, 0, sizeof(long) * (size_t)B);
-            std::vector<int> seen(B, 0);
-            OCTA_HIP_CHECK(hipMemsetAsync(P.next_sample, 0, sizeof(int), stream));
-            // this launch's ticket and its sign-in counter (csrc/sim_api.cpp): the counter of the launch before the previous one is reused
-            M.launch_flag = octa_sim_launch_flag(S->ctx->device);
-            M.ticket = (int)(octa_sim_next_ticket() & 0x3fffffff);
-            if (M.launch_flag) {
-                OCTA_HIP_CHECK(hipMemsetAsync(M.launch_flag + 1 + (M.ticket & 1), 0, sizeof(int), stream));
-                OCTA_HIP_CHECK(hipMemsetAsync(M.launch_flag + 3 + (M.ticket & 1), 0, sizeof(int), stream));
-            }
-            S->last_ticket = M.ticket;
-            OCTA_HIP_CHECK(hipEventRecord(S->ev[0], stream));
-            const int grid = B < S->grid_cap ? B : S->grid_cap;
-            hipLaunchKernelGGL(sim_persistent_kernel, dim3((unsigned)grid), dim3(SIM_THREADS), SIM_LDS, stream, P, M);
-            OCTA_HIP_CHECK(hipGetLastError());
-            OCTA_HIP_CHECK(hipEventRecord(S->ev[1], stream));
-            launches++;
-            long idle = 0;
-            auto last_progress = clk::now(), iter_start = last_progress;
-            int last_done = 0;
-            while (true) {
-                {   // longest single pass of this loop, whatever it was spent in (callback, descheduling, ...)
-                    const auto t = clk::now();
-                    const double it_ms = std::chrono::duration<double, std::milli>(t - iter_start).count();
-                    if (it_ms > S->diag_max_gap_ms) S->diag_max_gap_ms = it_ms;
-                    if (mail_diag) pass_hist[it_ms < 0.01 ? 0 : it_ms < 0.03 ? 1 : it_ms < 0.1 ? 2 : it_ms < 0.3 ? 3 : it_ms < 1.0 ? 4 : 5]++;
-                    iter_start = t;
-                }
-                bool any = false;
-                S->diag_passes++;
-                for (int s = 0; s < B; s++) {
-                    const int t = __atomic_load_n(M.req_ticket + s, __ATOMIC_ACQUIRE);
-                    if (t == seen[s]) continue;
-                    any = true;
-                    if (S->test_stall_ms > 0 && !stalled_once) {   // test hook: the host goes away once, with a ticket pending
-                        stalled_once = true;
-                        std::this_thread::sleep_for(std::chrono::milliseconds(S->test_stall_ms));
-                    }
-                    const auto h_seen = clk::now();
-                    answer(s, __atomic_load_n(M.req_n + s, __ATOMIC_RELAXED));
-                    __atomic_store_n(M.resp_ticket + s, t, __ATOMIC_RELEASE);
-                    if (mail_diag) {      // host clock at sighting / answer against the device's publication stamp (clock offset = the smallest difference seen)
-                        const double d = std::chrono::duration<double, std::micro>(h_seen - wall0).count() - (double)__atomic_load_n(M.req_time + s, __ATOMIC_RELAXED) * 1e-2;
-                        if (d < diag_min_d) diag_min_d = d;
-                        diag_sum_serv += std::chrono::duration<double, std::micro>(clk::now() - h_seen).count();
-                        diag_lat.push_back(d);
-                    }
-                    seen[s] = t;
-                    S->diag_tickets++;
-                }
-                const int done = __atomic_load_n(M.done, __ATOMIC_ACQUIRE);
-                if (done >= B) break;
-                if (any || done != last_done) { idle = 0; last_done = done; last_progress = clk::now(); continue; }
-                if ((++idle & 63) == 0) {
-                    const double silent = std::chrono::duration<double, std::milli>(clk::now() - last_progress).count();
-                    if (silent > 1.0) {
-                        hipError_t q = hipEventQuery(S->ev[1]);
-                        if (q == hipSuccess) break;                       // launch over although not every sign-off was seen
-                        if (q != hipErrorNotReady) { octa::set_error("octa_sim_run: kernel failed: %s", hipGetErrorString(q)); return -1; }
-                        if (silent > 1000.0 * 120.0) { octa::set_error("octa_sim_run: the simulation kernel made no progress for 120 s"); return -1; }
-                    }
-                    if (idle > S->spin_scans) std::this_thread::sleep_for(std::chrono::microseconds(20));
-                }
-            }
-            float ms = 0;
-            OCTA_HIP_CHECK(hipEventSynchronize(S->ev[1]));
-            OCTA_HIP_CHECK(hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
-            ms_kernels += ms;
-            // kernel boundary: everything the launch wrote is visible now
-            OCTA_HIP_CHECK(hipMemcpyAsync(S->h_sc.data(), P.sc, sizeof(SampleScalars) * B, hipMemcpyDeviceToHost, stream));
-            OCTA_HIP_CHECK(hipStreamSynchronize(stream));
-            int n_parked = 0;
-            for (int s = 0; s < B; s++) {
-                if (!S->h_sc[s].parked || S->h_sc[s].err) continue;
-                n_parked++;
-                answer(s, M.req_n[s]);
-            }
-            if (n_parked == 0) break;
-            S->diag_relaunches++;
-            S->diag_parked += n_parked;
-            if (launches > 4 * (int)S->iters.size() + 16) { octa::set_error("octa_sim_run: %d launches without finishing (parking loop)", launches); return -1; }
-        }
-        const float ms = (float)ms_kernels;
-        S->ms_b = ms; S->n_b = launches;
-        if (mail_diag) {
-            fprintf(stderr, "[octa] mailbox service: %ld passes over %d tickets in %.1f ms of kernel (%.2f us per pass; <10 us %ld, <30 %ld, <100 %ld, <300 %ld, <1000 %ld, longer %ld; longest %.3f ms), "
-                            "%ld tickets, %.1f ms in the callback\n", S->diag_passes, B, ms_kernels, 1e3 * ms_kernels / (double)(S->diag_passes ? S->diag_passes : 1),
-                    pass_hist[0], pass_hist[1], pass_hist[2], pass_hist[3], pass_hist[4], pass_hist[5], S->diag_max_gap_ms, S->diag_tickets, S->ms_host_bif);
-            if (!diag_lat.empty() && S->mail.req_time[0] != 0) {
-                long h[7] = {0, 0, 0, 0, 0, 0, 0};
-                double sum = 0;
-                for (double d : diag_lat) { const double x = d - diag_min_d; sum += x; h[x < 10 ? 0 : x < 30 ? 1 : x < 100 ? 2 : x < 300 ? 3 : x < 1000 ? 4 : x < 3000 ? 5 : 6]++; }
-                fprintf(stderr, "[octa]   publication (device clock) -> seen by the host, above the fastest ticket: %.1f us on average (<10 us %ld, <30 %ld, <100 %ld, <300 %ld, <1000 %ld, <3000 %ld, "
-                                "longer %ld); seen -> answered %.1f us\n", sum / (double)diag_lat.size(), h[0], h[1], h[2], h[3], h[4], h[5], h[6], diag_sum_serv / (double)diag_lat.size());
-            }
-        }
-    } else
-    for (int it = 0; it <= C.n_iter; it++) {
+    for (int it = 0; it <= S->C.n_iter; it++) {
         float ms = 0;
-        OCTA_HIP_CHECK(hipEventRecord(S->ev[0], stream));
+        OCTA_HIP_CHECK(hipEventRecord(S->ev[0].h, stream));
         hipLaunchKernelGGL(sim_iter_a_kernel, dim3((unsigned)B), dim3(SIM_THREADS), SIM_LDS, stream, P, it, it > 0 ? 1 : 0);
         OCTA_HIP_CHECK(hipGetLastError());
-        OCTA_HIP_CHECK(hipEventRecord(S->ev[1], stream));
-        if (it == C.n_iter) {
-            OCTA_HIP_CHECK(hipEventSynchronize(S->ev[1]));
-            OCTA_HIP_CHECK(hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
+        OCTA_HIP_CHECK(hipEventRecord(S->ev[1].h, stream));
+        if (it == S->C.n_iter) {
+            OCTA_HIP_CHECK(hipEventSynchronize(S->ev[1].h));
+            OCTA_HIP_CHECK(hipEventElapsedTime(&ms, S->ev[0].h, S->ev[1].h));
             S->ms_a += ms; S->n_a++;
             break;
         }
         if (serve(0)) return -1;
-        OCTA_HIP_CHECK(hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
+        OCTA_HIP_CHECK(hipEventElapsedTime(&ms, S->ev[0].h, S->ev[1].h));
         S->ms_a += ms; S->n_a++;
-        OCTA_HIP_CHECK(hipEventRecord(S->ev[0], stream));
+        OCTA_HIP_CHECK(hipEventRecord(S->ev[0].h, stream));
         hipLaunchKernelGGL(sim_iter_b_kernel, dim3((unsigned)B), dim3(SIM_THREADS), SIM_LDS, stream, P, it);
         OCTA_HIP_CHECK(hipGetLastError());
-        OCTA_HIP_CHECK(hipEventRecord(S->ev[1], stream));
+        OCTA_HIP_CHECK(hipEventRecord(S->ev[1].h, stream));
         if (serve(1)) return -1;
-        OCTA_HIP_CHECK(hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
+        OCTA_HIP_CHECK(hipEventElapsedTime(&ms, S->ev[0].h, S->ev[1].h));
         S->ms_b += ms; S->n_b++;
     }
-    S->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    if (S->lockstep) {                   // (the persistent form has fetched the samples' scalars at its last kernel boundary)
-        S->h_sc.resize(B);
-        OCTA_HIP_CHECK(hipMemcpyAsync(S->h_sc.data(), P.sc, sizeof(SampleScalars) * B, hipMemcpyDeviceToHost, stream));
-        OCTA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    S->ran = true;
-#ifdef OCTA_SIM_DEBUG_SAT
-    if (const char *path = getenv("OCTA_SIM_DEBUG_DUMP")) {
-        std::vector<int> h((size_t)B * S->iters.size() * 16);
-        OCTA_HIP_CHECK(hipMemcpy(h.data(), P.dbg, h.size() * sizeof(int), hipMemcpyDeviceToHost));
-        if (FILE *fp = fopen(path, "wb")) { fwrite(h.data(), sizeof(int), h.size(), fp); fclose(fp); }
-    }
-#endif
-    for (int s = 0; s < B; s++)
+    S->h_sc.resize(B);
+    OCTA_HIP_CHECK(hipMemcpyAsync(S->h_sc.data(), P.sc, sizeof(SampleScalars) * B, hipMemcpyDeviceToHost, stream));
+    OCTA_HIP_CHECK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// The first sample that ended with capacity / error bits decides the run's result (-3); a device-side mailbox timeout of the persistent form
+// is reported with everything both sides know about that wait.
+int report_errors(const Sim *S) {
+    for (int s = 0; s < S->B; s++)
         if (S->h_sc[s].err) {
-            if ((S->h_sc[s].err & ERR_HOST_TIMEOUT) && !S->lockstep)
+            if ((S->h_sc[s].err & ERR_HOST_TIMEOUT) && !S->knobs.lockstep)
                 octa::set_error("octa_sim_run: sample %d failed with capacity/error bits 0x%x: with parking disabled (OCTA_SIM_PARK_MS=0) a workgroup waited "
                                 "more than %.0f ms for the host's mailbox answer (request ticket %d, answered %d, %ld tickets served this run, longest pass of the "
                                 "service loop %.1f ms, longest bifurcation callback %.1f ms; the workgroup began waiting for ticket %ld at %.1f ms into its "
                                 "launch, polled %ld times, at its deadline read answer %ld and its own request word back as %ld)", s, S->h_sc[s].err,
-                                S->mail_timeout_ms, S->mail.req_ticket[s], S->mail.resp_ticket[s], S->diag_tickets, S->diag_max_gap_ms, S->diag_max_bif_ms,
+                                S->knobs.mail_timeout_ms, S->mail.req_ticket[s], S->mail.resp_ticket[s], S->svc.tickets, S->svc.max_gap_ms, S->svc.max_bif_ms,
                                 S->h_sc[s].prof[13], S->h_sc[s].prof[12] * 1e-5, S->h_sc[s].prof[14], S->h_sc[s].prof[11], S->h_sc[s].prof[15]);
             else
                 octa::set_error("octa_sim_run: sample %d failed with capacity/error bits 0x%x", s, S->h_sc[s].err);
@@ -1296,9 +1216,33 @@ int sim_run_impl(OCTA_SIM_T *S, const SampleSource &src, octa_bif_fn bif, void *
         }
     return 0;
 }
-}  // namespace
 
-extern "C" int octa_sim_edge_offsets(OCTA_SIM_T *S, int64_t *h_edge_off, int64_t *h_n_art) {
+int sim_run_impl(Sim *S, const SampleSource &src, octa_bif_fn bif, void *user, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    OCTA_HIP_CHECK(hipSetDevice(S->ctx->device));
+    {
+        SetupStage h(S);
+        const int bad = fill_samples(S->cfg, src, S->B, S->knobs.init_threads, h.st);
+        if (bad >= 0) { octa::set_error("octa_sim_run: sample %d has no valid voxel", bad); return -2; }
+        if (int rc = upload_samples(S, h, stream)) return rc;
+    }
+    S->ms_a = S->ms_b = S->ms_total = S->ms_host_bif = 0; S->n_a = S->n_b = S->n_bif_req = 0;
+    const auto wall0 = clk::now();
+    if (int rc = S->knobs.lockstep ? run_lockstep(S, bif, user, stream) : run_persistent(S, bif, user, stream, wall0)) return rc;
+    S->ms_total = ms_since(wall0);
+    S->ran = true;
+#ifdef OCTA_SIM_DEBUG_SAT
+    if (const char *path = getenv("OCTA_SIM_DEBUG_DUMP")) {
+        std::vector<int> h((size_t)S->B * S->iters.size() * 16);
+        OCTA_HIP_CHECK(hipMemcpy(h.data(), S->P.dbg, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+        if (FILE *fp = fopen(path, "wb")) { fwrite(h.data(), sizeof(int), h.size(), fp); fclose(fp); }
+    }
+#endif
+    return report_errors(S);
+}
+
+int sim_edge_offsets(void *impl, int64_t *h_edge_off, int64_t *h_n_art) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_edge_off) { octa::set_error("octa_sim_edge_offsets: run the simulation first"); return -2; }
     h_edge_off[0] = 0;
     for (int s = 0; s < S->B; s++) {
@@ -1310,7 +1254,8 @@ extern "C" int octa_sim_edge_offsets(OCTA_SIM_T *S, int64_t *h_edge_off, int64_t
     return 0;
 }
 
-extern "C" int octa_sim_export_edges(OCTA_SIM_T *S, double *h_edges) {
+int sim_export_edges(void *impl, double *h_edges) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_edges) { octa::set_error("octa_sim_export_edges: run the simulation first"); return -2; }
     OCTA_HIP_CHECK(hipSetDevice(S->ctx->device));
     const BatchPtrs &P = S->P;
@@ -1323,13 +1268,14 @@ extern "C" int octa_sim_export_edges(OCTA_SIM_T *S, double *h_edges) {
     size_t need = 0;
     for (int f = 0; f < 2; f++) need += (size_t)B * nmax[f] * (24 + 8 + 4 + 4 + 4 + 1) + 64 * 6;
     if (S->export_cap < need) {
-        if (S->export_stage) { hipError_t e = hipHostFree(S->export_stage); (void)e; S->export_stage = nullptr; S->export_cap = 0; }
-        OCTA_HIP_CHECK(hipHostMalloc(&S->export_stage, need + need / 4));
+        S->export_stage.reset();
+        S->export_cap = 0;
+        OCTA_HIP_CHECK(hipHostMalloc(&S->export_stage.h, need + need / 4));
         S->export_cap = need + need / 4;
     }
-    hipStream_t stream = S->export_stream;
-    if (!stream) { OCTA_HIP_CHECK(hipStreamCreateWithFlags(&S->export_stream, hipStreamNonBlocking)); stream = S->export_stream; }
-    char *base = static_cast<char *>(S->export_stage);
+    if (!S->export_stream.h) OCTA_HIP_CHECK(hipStreamCreateWithFlags(&S->export_stream.h, hipStreamNonBlocking));
+    hipStream_t stream = S->export_stream.h;
+    char *base = S->export_stage.as<char>();
     double *pos[2], *rad[2];
     int *par[2], *c0[2], *c1[2];
     unsigned char *nch[2];
@@ -1368,30 +1314,33 @@ extern "C" int octa_sim_export_edges(OCTA_SIM_T *S, double *h_edges) {
     return 0;
 }
 
-extern "C" int octa_sim_export_edges_device(OCTA_SIM_T *S, double *d_edges, void *stream_) {
+int sim_export_edges_device(void *impl, double *d_edges, void *stream_) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !d_edges) { octa::set_error("octa_sim_export_edges_device: run the simulation first"); return -2; }
     OCTA_HIP_CHECK(hipSetDevice(S->ctx->device));
     hipStream_t stream = (hipStream_t)stream_;
     const int B = S->B;
     std::vector<long> off(B + 1, 0);
     for (int s = 0; s < B; s++) off[s + 1] = off[s] + (S->h_sc[s].n_nodes[0] - S->cfg.n_trees) + (S->h_sc[s].n_nodes[1] - S->cfg.n_trees);
-    if (!S->d_edge_off) OCTA_HIP_CHECK(hipMalloc(&S->d_edge_off, sizeof(long) * (B + 1)));
-    OCTA_HIP_CHECK(hipMemcpyAsync(S->d_edge_off, off.data(), sizeof(long) * (B + 1), hipMemcpyHostToDevice, stream));
+    if (!S->d_edge_off.h) OCTA_HIP_CHECK(hipMalloc(&S->d_edge_off.h, sizeof(long) * (B + 1)));
+    OCTA_HIP_CHECK(hipMemcpyAsync(S->d_edge_off.h, off.data(), sizeof(long) * (B + 1), hipMemcpyHostToDevice, stream));
     OCTA_HIP_CHECK(hipStreamSynchronize(stream));     // `off` is a local; the copy is a few hundred bytes
     const size_t lds = OCTA_SIM_LARGE ? 2048 : 2048 + (size_t)NCAP * 2 * sizeof(idx_t);
-    hipLaunchKernelGGL(sim_export_kernel, dim3((unsigned)B, 2), dim3(256), lds, stream, S->P, S->d_edge_off, S->cfg.n_trees, d_edges);
+    hipLaunchKernelGGL(sim_export_kernel, dim3((unsigned)B, 2), dim3(256), lds, stream, S->P, S->d_edge_off.as<long>(), S->cfg.n_trees, d_edges);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-extern "C" int octa_sim_trace(OCTA_SIM_T *S, int32_t *h_trace) {
+int sim_trace(void *impl, int32_t *h_trace) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_trace) { octa::set_error("octa_sim_trace: run the simulation first"); return -2; }
     OCTA_HIP_CHECK(hipSetDevice(S->ctx->device));
     OCTA_HIP_CHECK(hipMemcpy(h_trace, S->P.trace, sizeof(int32_t) * (size_t)S->B * S->iters.size() * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
-extern "C" int octa_sim_stats(OCTA_SIM_T *S, int64_t *h_stats) {
+int sim_stats(void *impl, int64_t *h_stats) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_stats) { octa::set_error("octa_sim_stats: run the simulation first"); return -2; }
     for (int s = 0; s < S->B; s++) {
         const SampleScalars &sc = S->h_sc[s];
@@ -1405,21 +1354,23 @@ extern "C" int octa_sim_stats(OCTA_SIM_T *S, int64_t *h_stats) {
     return 0;
 }
 
-extern "C" int octa_sim_kd_paths(OCTA_SIM_T *S, int64_t *h_paths) {
+int sim_kd_paths(void *impl, int64_t *h_paths) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_paths) { octa::set_error("octa_sim_kd_paths: run the simulation first"); return -2; }
     for (int s = 0; s < S->B; s++)
         for (int k = 0; k < 3; k++) h_paths[3 * s + k] = S->h_sc[s].kd_path[k];
     return 0;
 }
 
-extern "C" int octa_sim_assign_paths(OCTA_SIM_T *S, int64_t *h_paths) {
+int sim_assign_paths(void *impl, int64_t *h_paths) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_paths) { octa::set_error("octa_sim_assign_paths: run the simulation first"); return -2; }
     for (int s = 0; s < S->B; s++) { h_paths[2 * s] = S->h_sc[s].assign_path[0]; h_paths[2 * s + 1] = S->h_sc[s].assign_path[1]; }
     return 0;
 }
 
-extern "C" int octa_sim_fields(OCTA_SIM_T *S, int sample, double *h_oxy, int64_t cap_oxy, int64_t *n_oxy, double *h_co2,
-                               int64_t cap_co2, int64_t *n_co2) {
+int sim_fields(void *impl, int sample, double *h_oxy, int64_t cap_oxy, int64_t *n_oxy, double *h_co2, int64_t cap_co2, int64_t *n_co2) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || sample < 0 || sample >= S->B) { octa::set_error("octa_sim_fields: bad arguments"); return -2; }
     OCTA_HIP_CHECK(hipSetDevice(S->ctx->device));
     const SampleScalars &sc = S->h_sc[sample];
@@ -1437,7 +1388,6 @@ extern "C" int octa_sim_fields(OCTA_SIM_T *S, int sample, double *h_oxy, int64_t
 }
 
 #if !OCTA_SIM_LARGE
-namespace {
 __global__ void __launch_bounds__(SIM_THREADS)
 sim_kat_kd_kernel(const double *pts, int n, const unsigned char *need, idx_t *out_idx, idx_t *out_rank, float *xy, double zlo, double zhi,
                   int flag_in_sign, int need_bits) {
@@ -1447,22 +1397,19 @@ sim_kat_kd_kernel(const double *pts, int n, const unsigned char *need, idx_t *ou
 }
 
 int kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t *h_indices, int flag_in_sign, int need_bits);
-}  // namespace
-
-extern "C" int octa_sim_kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t *h_indices) {
+int sim_kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t *h_indices) {
     if (!ctx || !h_pts || !h_indices || n < 0 || n > OCAP) { octa::set_error("octa_sim_kat_kd_order: bad arguments"); return -2; }
     return kat_kd_order(ctx, h_pts, n, h_need, h_indices, 0, 0xff);
 }
 
 // the form phase_satisfy_art calls: the need flag rides in the sign of x (every x >= 0), need_bits selects the bits of a need byte that count
-extern "C" int octa_sim_kat_kd_order_signflag(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t need_bits, int32_t *h_indices) {
+int sim_kat_kd_order_signflag(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t need_bits, int32_t *h_indices) {
     if (!ctx || !h_pts || !h_need || !h_indices || n < 0 || n > OCAP || need_bits <= 0 || need_bits > 0xff) { octa::set_error("octa_sim_kat_kd_order_signflag: bad arguments"); return -2; }
     for (int64_t i = 0; i < n; i++)
         if (!(h_pts[3 * i] >= 0.0)) { octa::set_error("octa_sim_kat_kd_order_signflag: x must be >= 0"); return -2; }
     return kat_kd_order(ctx, h_pts, n, h_need, h_indices, 1, need_bits);
 }
 
-namespace {
 int kat_kd_order(octa_ctx *ctx, const double *h_pts, int64_t n, const uint8_t *h_need, int32_t *h_indices, int flag_in_sign, int need_bits) {
     if (n == 0) return 0;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
@@ -1497,9 +1444,7 @@ sim_kat_sample_kernel(SimArrays A, SimConst C, IterParams P) {
     Blk b = {(int)threadIdx.x, (int)blockDim.x, smem};
     phase_sample(b, A, C, P, 0);
 }
-}  // namespace
-
-extern "C" int octa_sim_kat_sample(octa_ctx *ctx, const double *h_cand, int64_t n_cand, const double *h_npos, const double *h_nrad, int64_t n_art,
+int sim_kat_sample(octa_ctx *ctx, const double *h_cand, int64_t n_cand, const double *h_npos, const double *h_nrad, int64_t n_art,
                                    double *h_oxy, int64_t n_oxy, int64_t cap_oxy, double eps_n, double eps_k, double eps_s, const double *h_cst8,
                                    int64_t *h_n_out) {
     if (!ctx || !h_cst8 || !h_n_out || n_cand < 0 || n_cand > NCANDCAP || n_art < 0 || n_art > NCAP || n_oxy < 0 || n_oxy > OCAP || cap_oxy < n_oxy ||
@@ -1554,28 +1499,52 @@ extern "C" int octa_sim_kat_sample(octa_ctx *ctx, const double *h_cand, int64_t 
 
 #endif
 
-extern "C" int octa_sim_service_stats(OCTA_SIM_T *S, double *h_out4) {
+int sim_service_stats(void *impl, double *h_out4) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_out4) { octa::set_error("octa_sim_service_stats: run the simulation first"); return -2; }
-    h_out4[0] = (double)S->diag_tickets; h_out4[1] = S->diag_max_gap_ms; h_out4[2] = (double)S->diag_relaunches; h_out4[3] = (double)S->diag_parked;
-    h_out4[4] = S->diag_max_bif_ms;
+    h_out4[0] = (double)S->svc.tickets; h_out4[1] = S->svc.max_gap_ms; h_out4[2] = (double)S->svc.relaunches; h_out4[3] = (double)S->svc.parked;
+    h_out4[4] = S->svc.max_bif_ms;
     return 0;
 }
 
-extern "C" int octa_sim_geometry(int num_cus, int *h_out4) {
+int sim_geometry(int num_cus, int *h_out4) {
     if (!h_out4) { octa::set_error("octa_sim_geometry: null output"); return -2; }
     h_out4[0] = SIM_THREADS; h_out4[1] = SIM_WG_PER_CU; h_out4[2] = (int)SIM_LDS; h_out4[3] = SIM_WG_PER_CU * (num_cus > 0 ? num_cus : 256);
     return 0;
 }
 
-extern "C" int octa_sim_spans(OCTA_SIM_T *S, int64_t *h_spans) {
+int sim_spans(void *impl, int64_t *h_spans) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_spans) { octa::set_error("octa_sim_spans: run the simulation first"); return -2; }
     for (int s = 0; s < S->B; s++) { h_spans[2 * s] = S->h_sc[s].t_begin; h_spans[2 * s + 1] = S->h_sc[s].t_end; }
     return 0;
 }
 
-extern "C" int octa_sim_timing(OCTA_SIM_T *S, double *h_out8) {
+int sim_timing(void *impl, double *h_out8) {
+    Sim *S = sim_of(impl);
     if (!S || !S->ran || !h_out8) { octa::set_error("octa_sim_timing: run the simulation first"); return -2; }
     h_out8[0] = S->ms_a; h_out8[1] = (double)S->n_a; h_out8[2] = S->ms_b; h_out8[3] = (double)S->n_b;
     h_out8[4] = S->ms_total; h_out8[5] = S->ms_host_bif; h_out8[6] = (double)S->n_bif_req; h_out8[7] = (double)S->bytes;
     return 0;
 }
+
+#ifndef __HIP_DEVICE_COMPILE__     // host pass only: the table holds host function addresses and must not become a device-side object
+constexpr octa_sim_ops SIM_OPS = {
+    sim_create, sim_destroy, sim_run, sim_run_states, sim_np_state, sim_edge_offsets, sim_export_edges, sim_export_edges_device, sim_trace, sim_stats,
+    sim_kd_paths, sim_assign_paths, sim_spans, sim_timing, sim_service_stats, sim_fields, sim_geometry,
+#if !OCTA_SIM_LARGE
+    sim_kat_kd_order, sim_kat_kd_order_signflag, sim_kat_sample,
+#endif
+};
+#endif
+
+}  // namespace
+
+// the one symbol this build exports (csrc/sim_ops.h)
+#ifndef __HIP_DEVICE_COMPILE__
+#if OCTA_SIM_LARGE
+extern "C" const octa_sim_ops octa_simL_ops = SIM_OPS;
+#else
+extern "C" const octa_sim_ops octa_simS_ops = SIM_OPS;
+#endif
+#endif

@@ -1,5 +1,6 @@
 // sim_host.h -- host-side pieces of the simulator: RNG streams, per-sample initialisation, the
-// per-iteration parameter table, and the BFS edge export. Plain C++ (no HIP).
+// per-iteration parameter table, the BFS edge export, the run-time knobs (SimKnobs) and the threaded
+// per-batch set-up (fill_samples). Plain C++ (no HIP).
 //
 //   numpy legacy RandomState / CPython random streams   
 //   Greenhouse.__init__, init_params_from_config          greenhouse.py:17-51
@@ -9,9 +10,12 @@
 //   edge list order                                       generate_vessel_graph.py:43-56
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 #include "sim_core.h"
@@ -358,6 +362,129 @@ inline long export_edges(const double *npos[2], const double *nrad[2], const int
         (void)n_nodes;
     }
     return ne;
+}
+
+// ---- run-time knobs of the simulator: every environment variable the host side reads, read ONCE per simulator (octa_sim_create).
+// OCTA_SIM_BUILD is not here: csrc/sim_api.cpp reads it to choose between the two builds before either exists.
+struct SimKnobs {
+    bool lockstep = false;          // OCTA_SIM_LOCKSTEP=1: two launches per iteration (the round-1 form), kept as the comparison form
+    double mail_timeout_ms = 30000; // OCTA_SIM_MAIL_TIMEOUT_MS (>= 1): device-side bound on one wait for the host when parking is off
+    double park_ms = 100.0;         // OCTA_SIM_PARK_MS (>= 0): a workgroup that has waited this long for its answer parks (0: never). Normal answers
+                                    // take tens of microseconds; 3 ms (until the end of round 2) also parked workgroups whenever a busy host
+                                    // descheduled the service thread for a few milliseconds, and a park costs a drain + relaunch. Round 6:
+                                    // 20 -> 100 ms. A parked sample is re-run ALONE at the launch's end (+400 ms for a 512-sample launch);
+                                    // one headline run in ~16 lost a launch that way to a host stall of a few tens of milliseconds, which
+                                    // costs its own length when it is waited out. The episodes parking exists for (a launch whose tickets
+                                    // the host stops seeing) take 80 ms longer to resolve.
+    int grid_cap = 512;             // OCTA_SIM_GRID (>= 1): workgroups per launch of the persistent kernel; default: the caller's (SIM_WG_PER_CU per CU)
+    int test_stall_ms = 0;          // OCTA_SIM_TEST_HOST_STALL_MS (test hook): the service thread sleeps once with a ticket pending
+    long spin_scans = 4096;         // OCTA_SIM_SPIN_SCANS: idle mailbox scans before the service thread starts sleeping 20 us between scans. Several
+                                    // ranks per host (WORLD_SIZE > 1; one service thread per step in flight and rank) give the cores back sooner: 256
+    int alloc_mode = 0;             // OCTA_SIM_ALLOC=finegrained (1) | uncached (2), experiment knob (DESIGN.md 4.1 "Open"): places the simulator's HBM
+                                    // state in fine-grained / uncached device memory (other MTYPE: other caching rules of the vector L1 and the L2)
+    int init_threads = 1;           // OCTA_SIM_INIT_THREADS (1..64): host threads of fill_samples. Default: half of this rank's share of the host
+                                    // (hardware threads / (2 * WORLD_SIZE)), at most 8 -- the service threads and the trainer need the rest
+    bool mail_diag = false;         // OCTA_SIM_MAIL_DIAG set (tools/sim_mailbox_profile.py): what a ticket waits for, from the host's side, on stderr
+                                    // -- passes of the service loop, and, with a -DOCTA_SIM_PROF_MAIL library, the device's publication stamp
+                                    // against the host's clock
+};
+
+inline SimKnobs read_knobs(int default_grid) {
+    SimKnobs k;
+    int world = 1;
+    if (const char *e = getenv("WORLD_SIZE")) { const int v = atoi(e); if (v > 1) world = v; }
+    const char *ls = getenv("OCTA_SIM_LOCKSTEP");
+    k.lockstep = ls && ls[0] == '1';
+    if (const char *e = getenv("OCTA_SIM_MAIL_TIMEOUT_MS")) { double v = atof(e); if (v >= 1.0) k.mail_timeout_ms = v; }
+    if (const char *e = getenv("OCTA_SIM_TEST_HOST_STALL_MS")) k.test_stall_ms = atoi(e);
+    if (const char *e = getenv("OCTA_SIM_PARK_MS")) { double v = atof(e); if (v >= 0.0) k.park_ms = v; }
+    k.grid_cap = default_grid;
+    if (const char *e = getenv("OCTA_SIM_GRID")) { int v = atoi(e); if (v >= 1) k.grid_cap = v; }
+    if (world > 1) k.spin_scans = 256;
+    if (const char *e = getenv("OCTA_SIM_SPIN_SCANS")) k.spin_scans = atol(e);
+    if (const char *e = getenv("OCTA_SIM_ALLOC")) k.alloc_mode = !strcmp(e, "finegrained") ? 1 : (!strcmp(e, "uncached") ? 2 : 0);
+    const int hw = (int)std::thread::hardware_concurrency() / (2 * world);
+    k.init_threads = hw < 1 ? 1 : (hw > 8 ? 8 : hw);
+    if (const char *e = getenv("OCTA_SIM_INIT_THREADS")) { const int v = atoi(e); if (v >= 1) k.init_threads = v < 64 ? v : 64; }
+    k.mail_diag = getenv("OCTA_SIM_MAIL_DIAG") != nullptr;
+    return k;
+}
+
+// what differs between the entry points: how sample s gets its FAZ radius, stump nodes and generator states
+struct SampleSource {
+    const uint32_t *np_seeds = nullptr;
+    const uint64_t *py_seeds = nullptr;
+    const double *faz = nullptr, *stumps = nullptr;        // [B], [B][2][2 * n_trees][3]
+    const uint32_t *np_states = nullptr, *py_states = nullptr;   // [B][625] each: 624 words + position
+    void fill(const SimConfig &cfg, int s, SampleInit *I) const {
+        if (np_seeds) { init_sample(cfg, np_seeds[s], py_seeds[s], I); return; }
+        Mt19937 np, py;
+        memcpy(np.mt, np_states + (size_t)s * 625, 624 * 4); np.idx = (int)np_states[(size_t)s * 625 + 624];
+        memcpy(py.mt, py_states + (size_t)s * 625, 624 * 4); py.idx = (int)py_states[(size_t)s * 625 + 624];
+        const size_t n = (size_t)2 * cfg.n_trees * 3;
+        init_sample_given(cfg, faz[s], stumps + (size_t)s * 2 * n, stumps + (size_t)s * 2 * n + n, np, py, I);
+    }
+};
+
+// where fill_samples leaves a batch's set-up; the caller owns every array
+struct SampleStaging {
+    SampleScalars *sc = nullptr;            // [B]
+    unsigned *np_state = nullptr;           // [B][625] numpy's generator behind the stumps: 624 words + position
+    unsigned *py_state = nullptr;           // [B][625] CPython's
+    unsigned short *valid = nullptr;        // [B][valid_stride] (i, j, k) per valid voxel; entries behind a sample's count are never read
+    size_t valid_stride = 0;                // 0: one list for all samples (geometry file), nothing is written
+    unsigned *valid_count = nullptr;        // [B]
+    double *stumps = nullptr;               // [B][2][2 * n_trees][3] stump nodes of the two forests
+};
+
+// The large staging arrays (18 MB of valid-voxel lists, 2.6 MB of generator states for 512 samples) live in ONE pinned block that a simulator
+// keeps: allocated and zero-filled per run they cost ~3 ms of page faults and a pageable copy, between two kernels. Layout: the voxel lists,
+// padded to 256 B, then numpy's and CPython's generator states. Returns the block's size; given a block, points `st` into it.
+inline size_t stage_layout(int B, size_t valid_stride, void *block = nullptr, SampleStaging *st = nullptr) {
+    const size_t n_mt = (size_t)B * 625, valid_bytes = ((size_t)B * valid_stride * 2 + 255) & ~(size_t)255;
+    if (block) {
+        st->valid = static_cast<unsigned short *>(block);
+        st->valid_stride = valid_stride;
+        st->np_state = reinterpret_cast<unsigned *>(static_cast<char *>(block) + valid_bytes);
+        st->py_state = st->np_state + n_mt;
+    }
+    return valid_bytes + 2 * n_mt * 4;
+}
+
+// Host set-up of every sample of a batch (FAZ radius, validity mask, stumps, RNG streams) into `st`. Pure host code, no HIP call. The samples
+// are independent, so a few threads share them in contiguous ranges (round 5: 5.6 of the 6.9 ms the set-up takes for 512 samples were this
+// loop on one core, and it sits between two persistent kernels of the pipeline): a second thread from 64 samples on, at most one per 32
+// samples and `n_threads` in all; the caller's thread takes the first range. Returns -1, or the first sample found without a valid voxel
+// (its voxel list, CPython state and stumps are then not written).
+inline int fill_samples(const SimConfig &cfg, const SampleSource &src, int B, int n_threads, const SampleStaging &st) {
+    const int n0 = 2 * cfg.n_trees;
+    std::atomic<int> bad_sample{-1};
+    auto fill_range = [&](int s_begin, int s_end) {
+        SampleInit I;
+        I.want_py_u = false;             // the uniforms are drawn on the device from the generator state (py_uniform_kernel)
+        for (int s = s_begin; s < s_end; s++) {
+            src.fill(cfg, s, &I);
+            memset(&st.sc[s], 0, sizeof(SampleScalars));
+            st.sc[s].faz_radius = I.faz_radius;
+            st.sc[s].py_cap = PYCAP;
+            st.sc[s].n_nodes[0] = st.sc[s].n_nodes[1] = n0;
+            memcpy(&st.np_state[(size_t)s * 625], I.np_state.mt, 624 * 4);
+            st.np_state[(size_t)s * 625 + 624] = (unsigned)I.np_state.idx;
+            st.valid_count[s] = (unsigned)(I.valid.size() / 3);
+            if (st.valid_count[s] == 0) { int none = -1; bad_sample.compare_exchange_strong(none, s); continue; }
+            if (st.valid_stride) memcpy(&st.valid[(size_t)s * st.valid_stride], I.valid.data(), I.valid.size() * 2);
+            memcpy(&st.py_state[(size_t)s * 625], I.py_state.mt, 624 * 4);
+            st.py_state[(size_t)s * 625 + 624] = (unsigned)I.py_state.idx;
+            for (int f = 0; f < 2; f++) memcpy(&st.stumps[((size_t)s * 2 + f) * n0 * 3], I.pos[f].data(), sizeof(double) * n0 * 3);
+        }
+    };
+    const int nt = B >= 64 ? (n_threads < B / 32 ? n_threads : B / 32) : 1;
+    std::vector<std::thread> pool;
+    const int per = (B + nt - 1) / nt;
+    for (int t = 1; t < nt; t++) pool.emplace_back(fill_range, t * per < B ? t * per : B, (t + 1) * per < B ? (t + 1) * per : B);
+    fill_range(0, per < B ? per : B);
+    for (auto &th : pool) th.join();
+    return bad_sample.load();
 }
 
 }  // namespace OCTA_SIMK

@@ -379,3 +379,46 @@ def test_lockstep_and_persistent_forms_agree(gh, golden, monkeypatch):
     assert a.timing["launches_a"] == 0 and b.timing["launches_a"] > 0
     assert (a.edge_off == b.edge_off).all()
     assert a.edges.tobytes() == b.edges.tobytes()
+
+
+def test_create_refusals_free_everything_and_keep_their_messages(gh, golden):
+    """Every refusal of octa_sim_create that one mutation of a valid short configuration reaches returns -2 with its message and leaves a
+    library in which the smallest fixture can still be created and run. Argument checking only: no case reaches a kernel launch."""
+    import ctypes
+    from octa_autosegmentation_amd import _native
+    lib, ctx = _native.lib(), _native.ctx()
+    seed, i1, i2 = (int(v) for v in golden["run_s11_20_0_seed_I"])
+    cfg = _cfg(golden, i1, i2)
+    mask = np.ones((76, 76, 1), np.uint8)
+
+    def n_modes_0(p): p.n_modes = 0
+    def seven_walls(p): p.n_source_walls = 7
+    def wall_9(p): p.source_walls[0] = 9
+    def z_wall(p): p.source_walls[0] = 4
+    def geometry_dim_0(p): p.geometry = mask.ctypes.data; p.geometry_shape[0], p.geometry_shape[1], p.geometry_shape[2] = 0, 76, 1
+    def forest_type_2(p): p.forest_type = 2
+    def too_many_candidates(p): p.modes[0][1] = 8193.0
+    def no_wall(p):
+        p.n_source_walls = 0
+        for w in range(4):
+            p.walls[w] = 0
+    def wide_space(p): p.size[0] = 1.5
+
+    cases = [(n_modes_0, "octa_sim_create: n_modes must be 1..8"),
+             (seven_walls, "octa_sim_create: n_source_walls must be 0..6"),
+             (wall_9, "octa_sim_create: source_walls[0] = 9 is not a wall (0..5)"),
+             (z_wall, "octa_sim_create: the z source walls need a sampling geometry file (the reference fails without one)"),
+             (geometry_dim_0, "octa_sim_create: sampling geometry [0][76][1]: every dimension must be 1..65535 and the mask at most 2^26 voxels"),
+             (forest_type_2, "octa_sim_create: forest_type must be 0 (stumps) or 1 (nerve)"),
+             (too_many_candidates, "octa_sim_create: N=8193 exceeds 8192"),
+             (no_wall, "octa_sim_create: bad forest config"),
+             (wide_space, "octa_sim_create: simulation space larger than the unit square")]
+    for mutate, message in cases:
+        p = gh.config_to_struct(cfg)
+        mutate(p)
+        h = ctypes.c_void_p()
+        rc = lib.octa_sim_create_ex(ctx, ctypes.byref(p), 2, 1, ctypes.byref(h))      # build 1: the default build, whatever OCTA_SIM_BUILD says
+        assert rc == -2 and not h.value, (mutate.__name__, rc)
+        assert lib.octa_last_error().decode() == message, mutate.__name__
+    res = gh.simulate_batch(cfg, [seed])
+    assert gh.edges_to_csv_text(res.sample_edges(0)).encode() == golden["run_s11_20_0_csv"].tobytes()
