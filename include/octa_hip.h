@@ -17,8 +17,11 @@
  *    the default stream) and returns without synchronising unless stated.
  *  - return value: 0 = ok, <0 = error; octa_last_error() gives the message of the
  *    last failure on the calling thread. Functions never throw.
- *  - an octa_ctx owns grow-only scratch in HBM for one device; use one ctx per
- *    process/GPU. A ctx is not safe for concurrent use from two threads.
+ *  - an octa_ctx owns grow-only scratch in HBM for one device and serves one
+ *    stream at a time; it is not safe for concurrent use from two threads. Most
+ *    of the scratch is work space whose contents are dead when an entry point
+ *    returns, so entry points may follow each other on a ctx in any order. The
+ *    one state that lives from call to call is the rasteriser's plan (below).
  *  - all simulator / rasteriser arithmetic is IEEE double or integer; device code
  *    is compiled with -ffp-contract=off.
  */
@@ -47,7 +50,7 @@ const char *octa_last_error(void);
 int octa_ctx_create(int device, octa_ctx **out);
 void octa_ctx_destroy(octa_ctx *ctx);
 
-/* Bytes of device scratch currently held by the context. */
+/* Bytes of device scratch currently held by the context: every buffer it owns. */
 size_t octa_ctx_scratch_bytes(const octa_ctx *ctx);
 
 /* ---- N5: 2-D anti-aliased graph rasteriser ------------------------------
@@ -77,7 +80,9 @@ int octa_rasterize_2d(octa_ctx *ctx, int B, const double *d_edges, const int64_t
  * batch while the persistent simulator kernel of the next one holds the CUs). _plan takes octa_rasterize_2d's arguments without d_out, runs
  * the per-edge records and the side-offset scan and performs the rasteriser's ONE host synchronisation (the side array is sized from the
  * scan total) and every scratch allocation; _draw enqueues tessellation, row binning and the ordered fold on `stream` and never waits for
- * the device. A context holds one plan: every _draw consumes the plan of the _plan before it (-2 without one). Same stream for both.
+ * the device. A context holds one plan: every _draw consumes the plan of the _plan before it (-2 without one), and a second _plan (or an
+ * octa_rasterize_2d) replaces the first. Any other entry point may run on the context between _plan and _draw, on the same stream; a call
+ * that needs more work space than the plan reserved makes that call, not the _draw, allocate.
  * octa_rasterize_2d(...) == _plan(...) followed by _draw(d_out). */
 int octa_rasterize_2d_plan(octa_ctx *ctx, int B, const double *d_edges, const int64_t *h_edge_off,
                            const uint8_t *d_keep, int no_pixels_x, int no_pixels_y, int mip_axis,

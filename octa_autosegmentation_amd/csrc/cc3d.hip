@@ -336,11 +336,10 @@ extern "C" int octa_cc3d_filter(octa_ctx *ctx, const uint8_t *d_in, int B, int D
     if (d_in < d_out + n_total && d_out < d_in + n_total) { octa::set_error("octa_cc3d_filter: bad pointers (d_out overlaps d_in)"); return -2; }
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    if (ctx->r_tile_fill.reserve(sizeof(int) * (size_t)n_total)) return -1;
-    if (ctx->r_tile_list.reserve(sizeof(int) * (size_t)n_total)) return -1;
-    if (ctx->r_tile_total.reserve(sizeof(unsigned long long) * 2 * (size_t)B)) return -1;
-    int *Lg = ctx->r_tile_fill.as<int>(), *cnt = ctx->r_tile_list.as<int>();
-    unsigned long long *best = ctx->r_tile_total.as<unsigned long long>(), *ncomp = best + B;
+    int *Lg = ctx->work[2].take<int>((size_t)n_total), *cnt = ctx->work[1].take<int>((size_t)n_total);
+    unsigned long long *best = ctx->work[3].take<unsigned long long>(2 * (size_t)B);
+    if (!Lg || !cnt || !best) return -1;
+    unsigned long long *ncomp = best + B;
     const int nbx = (W + BX - 1) / BX, nby = (H + BY - 1) / BY, nbz = (D + BZ - 1) / BZ;
     const unsigned bricks = (unsigned)((long)nbx * nby * nbz * B);      // <= n_total
     const unsigned blocks = (unsigned)((n_total + NT - 1) / NT);

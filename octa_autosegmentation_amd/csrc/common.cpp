@@ -36,19 +36,7 @@ extern "C" void octa_ctx_destroy(octa_ctx *ctx) {
     if (!ctx) return;
     hipError_t e = hipSetDevice(ctx->device);
     (void)e;
-    ctx->r_edge_off.release();
-    ctx->r_ucount.release();
-    ctx->r_seg_total.release();
-    ctx->r_sides.release();
-    ctx->r_edge_meta.release();
-    ctx->r_tile_count.release();
-    ctx->r_tile_fill.release();
-    ctx->r_tile_total.release();
-    ctx->r_tile_list.release();
-    ctx->r_counters.release();
-    ctx->zero_page.release();
-    ctx->wgrad_ws.release();
-    ctx->zero_ring.release();
+    octa_ctx::each_buffer(*ctx, [](octa::DevBuf &b) { b.release(); });
     delete ctx;
 }
 

@@ -2,10 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/octa_hip.h"
@@ -58,6 +60,9 @@ struct DevBuf {
         cap = 0;
     }
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+    // room for `count` elements of T, then the buffer as T*; nullptr with the error set when the allocation fails
+    template <class T> T *take(size_t count) { return reserve(sizeof(T) * count) ? nullptr : as<T>(); }
+    DevBuf &operator=(const DevBuf &) = delete;    // an owner: assigning a struct that holds one (`plan = RasterPlan()`) must not compile
 };
 
 }  // namespace octa
@@ -75,25 +80,65 @@ __device__ __forceinline__ unsigned octa_pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ unsigned short octa_f2bf(float f) { return (unsigned short)(octa_pack_bf16x2(f, 0.f) & 0xffffu); }
 #endif
 
+namespace octa {
+
+// The rasteriser's device counters, zeroed by every plan. The kernels of raster.hip address them through `int *err_flag` (error at int 0,
+// the profile counters of an OCTA_RASTER_PROF build at ints 2 / 4 / 6) and `long *total_out`: the asserts below pin that layout.
+struct RasterCounters {
+    int error;          // a RasterError, 0 = none; written with atomicExch, the last writer wins
+    int pad;
+    long prof[3];       // 100 MHz ticks summed over workgroups: edge binning, stroke tessellation, ordered fold
+    long side_total;    // polygon sides of all edges: the plan half sizes the side array from it
+};
+static_assert(offsetof(RasterCounters, error) == 0 && offsetof(RasterCounters, prof) == 2 * sizeof(int) &&
+              offsetof(RasterCounters, prof[1]) == 4 * sizeof(int) && offsetof(RasterCounters, prof[2]) == 6 * sizeof(int) &&
+              offsetof(RasterCounters, side_total) == 4 * sizeof(long), "raster.hip's kernels index the counters as int 0, ints 2 / 4 / 6 and long 4");
+// Nothing in production reads `error` back: only octa_raster_prof returns it, to a timing tool ("Context scratch").
+enum RasterError {
+    RASTER_ERR_EDGE_SKIPPED = 1,    // a single edge does not fit the render workgroup's LDS pool and was left out
+    RASTER_ERR_TESS_OVERFLOW = 2,   // clipping gave an edge more extra side pieces than its spare slots hold; the surplus was dropped
+    RASTER_ERR_SIDE_TOTAL = 3,      // the side total left the 32-bit offset range
+};
+
+// HELD: what octa_rasterize_2d_plan leaves for octa_rasterize_2d_draw (raster.hip). A context holds one plan; only raster.hip names these.
+struct RasterPlan {
+    bool valid = false, rowbin = false; int B = 0, W = 0, H = 0; long n_total = 0;
+    DevBuf edge_off;   // long [B + 1]
+    DevBuf meta;        // EdgeMeta [n_total + 1]
+    DevBuf bbox;        // BBox16 [n_total + 1] per-edge pixel boxes
+    DevBuf side_off;    // int [n_total + 1] side offsets, local to a scan block
+    DevBuf block_sums;  // int [scan blocks + 1] scan block sums -> bases
+    DevBuf counters;    // RasterCounters
+};
+
+}  // namespace octa
+
 struct octa_ctx {
     int device = 0;
     int num_cus = 256;
-    // rasteriser scratch
-    octa::DevBuf r_edge_off;    // int64 [B+1]
-    octa::DevBuf r_ucount;      // int32 [n_total] upper bound of sides per edge -> local exclusive scan
-    octa::DevBuf r_seg_total;   // int64 [B] per-graph totals, then exclusive bases
-    octa::DevBuf r_sides;       // int4  [sum U]
-    octa::DevBuf r_edge_meta;   // EdgeMeta [n_total]
-    octa::DevBuf r_tile_count;  // int32 [B*ntiles] -> local exclusive scan
-    octa::DevBuf r_tile_fill;   // int32 [B*ntiles]
-    octa::DevBuf r_tile_total;  // int64 [B]
-    octa::DevBuf r_tile_list;   // int32 [sum tile counts]
-    octa::DevBuf r_counters;    // int64 [8] misc device counters
-    // what octa_rasterize_2d_plan left for octa_rasterize_2d_draw (raster.hip)
-    struct RasterPlan { bool valid = false, rowbin = false; int B = 0, W = 0, H = 0; long n_total = 0; } r_plan;
-    octa::DevBuf zero_page;     // 256 zero bytes: source of the padding pixels of the DMA-staged convolution (conv.hip)
-    octa::DevBuf wgrad_ws;      // per-workgroup partial weight gradients of conv3x3_nhwc_wgrad_tr_kernel (conv.hip), stream-ordered like the rest
-    // ring of pre-zeroed accumulator slots (norm.hip statistics): ONE memset per lap instead of one per launch. Stream-ordered
+    octa::RasterPlan plan;
+    // TRANSIENT: work buffers any entry point may take; their contents are dead once it returns (one context = one stream at a time).
+    //   0: rasteriser sides (int4), voxeliser byte volume
+    //   1: rasteriser row records (RowRec); component counts and roots (postproc, cc3d); skeleton pass flags
+    //   2: rasteriser per-row counts; component labels (postproc, cc3d); skeleton bit planes
+    //   3: fp64 partial sums (norm); best-component records (cc3d); voxeliser per-edge image index
+    // octa_rasterize_2d_plan RESERVES slots 0 - 2 for the draw half, which must not touch the allocator, and the draw half takes its
+    // pointers when it runs: only the capacity has to survive a call in between, and a grow-only buffer keeps that.
+    octa::DevBuf work[4];
+    octa::DevBuf wgrad_ws;      // TRANSIENT, kept apart from the slots: per-workgroup partial weight gradients (conv.hip, head.hip), stream-ordered like the rest
+    octa::DevBuf read_back_flag;  // TRANSIENT: int, octa_edges_read_back's count of unhandled rows (graphio.hip)
+    octa::DevBuf zero_page;     // HELD: 256 zero bytes: source of the padding pixels of the DMA-staged convolutions (conv.hip, conv_f32.hip)
+    // the zero page, filled on first use; nullptr on failure. `who` opens the error text
+    const void *zeros(const char *who) {
+        if (!zero_page.p) {
+            if (zero_page.reserve(256)) return nullptr;
+            // hipMemset on device memory may return before the fill has run, and it runs on the NULL stream, which torch's (non-blocking) streams do
+            // not wait for: the first DMA-staged launch of a fresh context could fetch its padding from an uncleared page. Wait for the device once.
+            if (hipMemset(zero_page.p, 0, zero_page.cap) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { octa::set_error("%s: zero page memset failed", who); zero_page.release(); return nullptr; }
+        }
+        return zero_page.p;
+    }
+    // HELD: ring of pre-zeroed accumulator slots (norm.hip statistics): ONE memset per lap instead of one per launch. Stream-ordered
     // like every other scratch buffer of the context (one context = one stream at a time).
     octa::DevBuf zero_ring;
     size_t zero_ring_pos = 0;
@@ -113,8 +158,15 @@ struct octa_ctx {
         zero_ring_pos += bytes;
         return r;
     }
+    // THE list of the context's device buffers: octa_ctx_destroy and scratch_bytes() walk it, so a new buffer is added here and nowhere else
+    template <class Ctx, class F> static void each_buffer(Ctx &c, F f) {
+        for (auto *b : {&c.plan.edge_off, &c.plan.meta, &c.plan.bbox, &c.plan.side_off, &c.plan.block_sums, &c.plan.counters, &c.work[0], &c.work[1],
+                        &c.work[2], &c.work[3], &c.wgrad_ws, &c.read_back_flag, &c.zero_page, &c.zero_ring})
+            f(*b);
+    }
     size_t scratch_bytes() const {
-        return r_edge_off.cap + r_ucount.cap + r_seg_total.cap + r_sides.cap + r_edge_meta.cap + r_tile_count.cap +
-               r_tile_fill.cap + r_tile_total.cap + r_tile_list.cap + r_counters.cap;
+        size_t n = 0;
+        each_buffer(*this, [&](const octa::DevBuf &b) { n += b.cap; });
+        return n;
     }
 };

@@ -41,15 +41,7 @@ constexpr int CONV_THREADS = 256;
 #endif
 
 // 256 zero bytes in HBM: the source of padding pixels for loads that must not be branched around
-const unsigned short *zero_page(octa_ctx *ctx) {
-    if (!ctx->zero_page.p) {
-        if (ctx->zero_page.reserve(256)) return nullptr;
-        // hipMemset on device memory may return before the fill has run, and it runs on the NULL stream, which torch's (non-blocking) streams do
-        // not wait for: the first DMA-staged launch of a fresh context could fetch its padding from an uncleared page. Wait for the device once.
-        if (hipMemset(ctx->zero_page.p, 0, ctx->zero_page.cap) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { octa::set_error("conv: zero page memset failed"); ctx->zero_page.release(); return nullptr; }
-    }
-    return ctx->zero_page.as<unsigned short>();
-}
+const unsigned short *zero_page(octa_ctx *ctx) { return static_cast<const unsigned short *>(ctx->zeros("conv")); }
 
 __device__ __forceinline__ unsigned short f2bf(float f) { return octa_f2bf(f); }
 
@@ -1527,8 +1519,8 @@ int launch_wgrad_tr(octa_ctx *ctx, const WgradLaunch &L) {
     constexpr int ws_from = 16;
     float *ws = nullptr;
     if (acc || (ws_from > 0 && per_block >= ws_from && per_block <= 64)) {      // acc: always through the workspace (wgrad_tr_acc_kernel folds it)
-        if (ctx->wgrad_ws.reserve((size_t)blocks * per_block * PAIRS_ * 9 * 32 * 32 * sizeof(float))) return -1;
-        ws = ctx->wgrad_ws.as<float>();
+        ws = ctx->wgrad_ws.take<float>((size_t)blocks * per_block * PAIRS_ * 9 * 32 * 32);
+        if (!ws) return -1;
     } else {
         OCTA_HIP_CHECK(hipMemsetAsync(dW, 0, sizeof(float) * 9 * (size_t)Cout * Cin, stream));
     }
@@ -1978,8 +1970,8 @@ extern "C" int octa_conv3x3_c1_wgrad(octa_ctx *ctx, const void *d_x, const void 
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     const int band = c1_band(ctx, N, H), bands = (H + band - 1) / band, parts = bands * N, total = Cout * 9;
-    if (ctx->wgrad_ws.reserve((size_t)parts * total * sizeof(float))) return -1;
-    float *ws = ctx->wgrad_ws.as<float>();
+    float *ws = ctx->wgrad_ws.take<float>((size_t)parts * total);
+    if (!ws) return -1;
     size_t lds = sizeof(float) * (size_t)(band + 2) * (W + 2);
     if (lds < sizeof(float) * 4 * total) lds = sizeof(float) * 4 * total;
     OCTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_c1_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

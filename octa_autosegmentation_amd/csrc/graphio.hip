@@ -119,8 +119,8 @@ extern "C" int octa_edges_read_back(octa_ctx *ctx, const double *d_edges, double
     if (n_edges <= 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    if (ctx->r_counters.reserve(sizeof(long) * 8)) return -1;
-    int *flag = ctx->r_counters.as<int>() + 14;
+    int *flag = ctx->read_back_flag.take<int>(1);
+    if (!flag) return -1;
     OCTA_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), stream));
     long n_vec = 2 * (long)n_edges;
     hipLaunchKernelGGL(read_back_kernel, dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0, stream, d_edges, d_out, n_vec, flag);

@@ -362,8 +362,8 @@ int launch_bwd(octa_ctx *ctx, const unsigned short *x, const unsigned short *dy,
     const long ntiles = (npix + HEAD_TP - 1) / HEAD_TP;
     const long blocks = ntiles < 2L * ctx->num_cus ? ntiles : 2L * ctx->num_cus;
     constexpr int KP = KT * 32, PSTRIDE = KP * CIN + KP;
-    if (ctx->wgrad_ws.reserve((size_t)blocks * PSTRIDE * sizeof(float))) return -1;
-    float *ws = ctx->wgrad_ws.as<float>();
+    float *ws = ctx->wgrad_ws.take<float>((size_t)blocks * PSTRIDE);
+    if (!ws) return -1;
     const size_t lds = (size_t)(KP + CIN) * HEAD_LD * sizeof(unsigned short);
     static_assert((size_t)PSTRIDE * sizeof(float) <= (size_t)(KP + CIN) * HEAD_LD * sizeof(unsigned short), "the wave reduction reuses the tile buffers");
     if (lds > 64 * 1024)      // 64 -> more than 32 channels: 66 KB of the CU's 160 KB

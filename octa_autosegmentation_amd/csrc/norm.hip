@@ -261,8 +261,8 @@ extern "C" int octa_instnorm_lrelu_fwd(octa_ctx *ctx, const void *d_x, void *d_y
     const long planes = (long)B * C;
     if (planes > 65535L * 16) { octa::set_error("octa_instnorm_lrelu_fwd: too many planes"); return -2; }
     const int splits = pick_splits(ctx, planes, hw);
-    if (ctx->r_tile_total.reserve(sizeof(double) * 2 * planes * splits)) return -1;
-    double *partial = ctx->r_tile_total.as<double>();
+    double *partial = ctx->work[3].take<double>(2 * planes * splits);
+    if (!partial) return -1;
     dim3 grid((unsigned)splits, (unsigned)planes);
     auto launch = [&](auto t) {   // t: an element of the activations' type
         typedef decltype(t) T;
@@ -284,8 +284,8 @@ extern "C" int octa_instnorm_lrelu_bwd(octa_ctx *ctx, const void *d_x, const voi
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
     const long planes = (long)B * C;
     const int splits = pick_splits(ctx, planes, hw);
-    if (ctx->r_tile_total.reserve(sizeof(double) * 2 * planes * splits)) return -1;
-    double *partial = ctx->r_tile_total.as<double>();
+    double *partial = ctx->work[3].take<double>(2 * planes * splits);
+    if (!partial) return -1;
     dim3 grid((unsigned)splits, (unsigned)planes);
     if (zero_affine_grads(d_dw, d_db, C, stream)) return -1;
     auto launch = [&](auto t) {   // t: an element of the activations' type
@@ -709,8 +709,8 @@ extern "C" int octa_instnorm_lrelu_nhwc_fwd(octa_ctx *ctx, const void *d_x, void
         hipLaunchKernelGGL(in_nhwc_fwd_apply, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, x, y, d_w, d_b, (long)hw, C, splits, d_stat_slots,
                            slope, eps, d_mean, d_rstd, 0, nslot, (long)B * C * 2);
     } else if (d_stat_partials) {
-        if (ctx->r_tile_total.reserve(sizeof(double) * 2 * (size_t)B * C)) return -1;
-        double *sums = ctx->r_tile_total.as<double>();
+        double *sums = ctx->work[3].take<double>(2 * (size_t)B * C);
+        if (!sums) return -1;
         hipLaunchKernelGGL(in_nhwc_fold_partials, dim3((unsigned)((C + 31) / 32), (unsigned)B), dim3(NT), 0, stream, d_stat_partials, tiles, C, sums);
         const int splits = nhwc_splits(ctx, B, hw);
         hipLaunchKernelGGL(in_nhwc_fwd_apply, dim3((unsigned)splits, (unsigned)B), dim3(NT), 0, stream, x, y, d_w, d_b, (long)hw, C, splits, sums, slope,

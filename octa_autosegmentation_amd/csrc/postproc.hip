@@ -108,9 +108,9 @@ extern "C" int octa_remove_small_objects(octa_ctx *ctx, const uint8_t *d_in, int
     if (n_total > 0x7fffffffL) { octa::set_error("octa_remove_small_objects: more than 2^31 pixels in one batch"); return -2; }
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    if (ctx->r_tile_fill.reserve(sizeof(int) * (size_t)n_total)) return -1;
-    if (ctx->r_tile_list.reserve(sizeof(int) * 2 * (size_t)n_total)) return -1;
-    int *L = ctx->r_tile_fill.as<int>(), *cnt = ctx->r_tile_list.as<int>(), *root = cnt + n_total;
+    int *L = ctx->work[2].take<int>((size_t)n_total), *cnt = ctx->work[1].take<int>(2 * (size_t)n_total);
+    if (!L || !cnt) return -1;
+    int *root = cnt + n_total;
     const unsigned blocks = (unsigned)((n_total + 255) / 256);
     hipLaunchKernelGGL(cc_init_kernel, dim3(blocks), dim3(256), 0, stream, d_in, L, cnt, n_total);
     // labels are global pixel indices, so images of a batch can never be united: neighbours are tested inside one image

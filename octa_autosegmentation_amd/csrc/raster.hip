@@ -10,7 +10,7 @@
 //  * raster_meta_kernel: one thread per edge runs the per-path double pipeline (radius filter,
 //    x1.3 width, data->display, Liang-Barsky clip, auto-snap) and emits a fixed 56-byte record
 //    + an int16 pixel bbox. No variable-size intermediate ever goes to HBM.
-//  * raster_render_kernel: one 1024-thread workgroup per 64x64 pixel super-tile. It streams the
+//  * raster_render_kernel: one 512-thread workgroup per 64x32 pixel super-tile (WG below). It streams the
 //    graph's bbox array (coalesced 8 B/edge), keeps the edges that touch the tile IN LIST ORDER
 //    with a ballot/prefix compaction into LDS, tessellates their stroke polygons into 24.8
 //    fixed-point sides in LDS (one thread per polygon side), then every wave owns a 16 x (4*NPX) block
@@ -374,7 +374,7 @@ __device__ __forceinline__ void block_scan2(int a, int b, int *sh /*[2*16+2]*/, 
 }
 
 // RB: the candidates come as records from raster_rowbin_kernel (the usual case); false: every edge of the graph is a candidate and its box,
-// side count and side offset are looked up here (graphs of 65 536 edges and more, OCTA_RASTER_ROWBIN=0). Two instantiations: the look-up
+// side count and side offset are looked up here (graphs of 65 536 edges and more, images of one row of super-tiles). Two instantiations: the look-up
 // path's three array pointers cost the record path scalar registers it spills
 #ifndef OCTA_RASTER_MIN_WGS
 #define OCTA_RASTER_MIN_WGS 1
@@ -1068,11 +1068,15 @@ __global__ void max_u8_kernel(const unsigned char *a, const unsigned char *b, un
 // side array is sized from the scan total) -- a few short kernels; _draw: tessellation, row binning and the ordered fold, enqueued
 // without touching the host or the allocator. A pipeline that shares the GPU with a long kernel plans while the GPU is free and draws
 // whenever it likes: nothing of the heavy part can end up queued behind a host wait (pipeline.py). octa_rasterize_2d = both.
+// What must survive from _plan to _draw lives in ctx->plan, which no other file names, so any other entry point may run on the context in between.
+enum { SIDES = 0, ROW_LIST = 1, ROW_CNT = 2 };   // the draw half's work slots (common.h)
+
 extern "C" int octa_rasterize_2d_plan(octa_ctx *ctx, int B, const double *d_edges, const int64_t *h_edge_off,
                                       const uint8_t *d_keep, int no_pixels_x, int no_pixels_y, int mip_axis,
                                       double min_radius, double max_radius, void *stream_) {
     if (!ctx) { octa::set_error("octa_rasterize_2d: null ctx"); return -2; }
-    ctx->r_plan = octa_ctx::RasterPlan();
+    octa::RasterPlan &plan = ctx->plan;
+    plan.valid = false;                         // a second plan replaces the first
     if (B <= 0) return 0;
     if (!h_edge_off) { octa::set_error("octa_rasterize_2d: null pointer"); return -2; }
     if (mip_axis < 0 || mip_axis > 2) { octa::set_error("octa_rasterize_2d: MIP_axis must be 0, 1 or 2"); return -2; }
@@ -1090,80 +1094,73 @@ extern "C" int octa_rasterize_2d_plan(octa_ctx *ctx, int B, const double *d_edge
     // tree2img.py:85: segment = ((cur[axes[1]], cur[axes[0]]), ...) -> x from axes[1], y from axes[0]
     const int ax_x = axes[1], ax_y = axes[0];
 
-    if (ctx->r_edge_off.reserve(sizeof(long) * (B + 1))) return -1;
-    if (ctx->r_edge_meta.reserve(sizeof(EdgeMeta) * (size_t)(n_total + 1))) return -1;
-    if (ctx->r_ucount.reserve(sizeof(BBox16) * (size_t)(n_total + 1))) return -1;
-    if (ctx->r_counters.reserve(sizeof(long) * 8)) return -1;
-    OCTA_HIP_CHECK(hipMemcpyAsync(ctx->r_edge_off.p, h_edge_off, sizeof(long) * (B + 1), hipMemcpyHostToDevice, stream));
-    OCTA_HIP_CHECK(hipMemsetAsync(ctx->r_counters.p, 0, sizeof(long) * 8, stream));
     const int nb = (int)((n_total + SCAN_BLK - 1) / SCAN_BLK);
-    if (ctx->r_tile_count.reserve(sizeof(int) * (size_t)(n_total + 1))) return -1;   // per-edge side offsets (block-local)
-    if (ctx->r_seg_total.reserve(sizeof(int) * (size_t)(nb + 1))) return -1;          // scan block sums -> bases
+    long *edge_off = plan.edge_off.take<long>(B + 1);
+    EdgeMeta *meta = plan.meta.take<EdgeMeta>((size_t)(n_total + 1));
+    BBox16 *bbox = plan.bbox.take<BBox16>((size_t)(n_total + 1));
+    octa::RasterCounters *counters = plan.counters.take<octa::RasterCounters>(1);
+    int *side_off = plan.side_off.take<int>((size_t)(n_total + 1));
+    int *block_sums = plan.block_sums.take<int>((size_t)(nb + 1));
+    if (!edge_off || !meta || !bbox || !counters || !side_off || !block_sums) return -1;
+    OCTA_HIP_CHECK(hipMemcpyAsync(edge_off, h_edge_off, sizeof(long) * (B + 1), hipMemcpyHostToDevice, stream));
+    OCTA_HIP_CHECK(hipMemsetAsync(counters, 0, sizeof(*counters), stream));
     long total_sides = 0;
     if (n_total > 0) {
         dim3 g((unsigned)((n_total + 255) / 256));
         hipLaunchKernelGGL(raster_meta_kernel, g, dim3(256), 0, stream, d_edges, d_keep, n_total, W, H, ax_x, ax_y,
-                           min_radius, max_radius, ctx->r_edge_meta.as<EdgeMeta>(), ctx->r_ucount.as<BBox16>());
-        hipLaunchKernelGGL(raster_scan_block_kernel, dim3((unsigned)nb), dim3(1024), 0, stream, ctx->r_edge_meta.as<EdgeMeta>(),
-                           n_total, ctx->r_tile_count.as<int>(), ctx->r_seg_total.as<int>());
-        hipLaunchKernelGGL(raster_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, ctx->r_seg_total.as<int>(), nb,
-                           ctx->r_counters.as<long>() + 4, ctx->r_counters.as<int>());
+                           min_radius, max_radius, meta, bbox);
+        hipLaunchKernelGGL(raster_scan_block_kernel, dim3((unsigned)nb), dim3(1024), 0, stream, meta, n_total, side_off, block_sums);
+        hipLaunchKernelGGL(raster_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, block_sums, nb, &counters->side_total, &counters->error);
         OCTA_HIP_CHECK(hipGetLastError());
         // the side array is sized from the scan total: one 8-byte read-back per call on this stream
-        OCTA_HIP_CHECK(hipMemcpyAsync(&total_sides, ctx->r_counters.as<long>() + 4, sizeof(long), hipMemcpyDeviceToHost, stream));
+        OCTA_HIP_CHECK(hipMemcpyAsync(&total_sides, &counters->side_total, sizeof(long), hipMemcpyDeviceToHost, stream));
         OCTA_HIP_CHECK(hipStreamSynchronize(stream));
         if (total_sides > 0x7fffffffL) { octa::set_error("octa_rasterize_2d: %ld polygon sides exceed the 32-bit offset range", total_sides); return -2; }
-        if (ctx->r_sides.reserve(sizeof(int4) * (size_t)(total_sides + 1))) return -1;
-    } else {
-        if (ctx->r_sides.reserve(sizeof(int4))) return -1;
     }
+    // the draw half's work buffers get their capacity here (the draw half must not touch the allocator) and their pointers there
+    if (ctx->work[SIDES].reserve(sizeof(int4) * (size_t)(total_sides + 1))) return -1;
     const int tiles_y = (H + ST_Y - 1) / ST_Y;
     // edges per row of super-tiles (u16 indices inside a graph): every graph must have fewer than 65 536 edges, and one row must be worth it
-    bool rowbin = false;
-    {
-        constexpr bool rowbin_on = true;
-        long max_graph = 0;
-        for (int b = 0; b < B; b++) max_graph = std::max<long>(max_graph, (long)(h_edge_off[b + 1] - h_edge_off[b]));
-        if (rowbin_on && n_total > 0 && tiles_y > 1 && max_graph < 65536) {
-            if (ctx->r_tile_list.reserve(sizeof(RowRec) * (size_t)n_total * tiles_y + 16)) return -1;
-            if (ctx->r_tile_fill.reserve(sizeof(int) * (size_t)B * tiles_y)) return -1;
-            rowbin = true;
-        }
+    long max_graph = 0;
+    for (int b = 0; b < B; b++) max_graph = std::max<long>(max_graph, (long)(h_edge_off[b + 1] - h_edge_off[b]));
+    const bool rowbin = n_total > 0 && tiles_y > 1 && max_graph < 65536;
+    if (rowbin) {
+        if (ctx->work[ROW_LIST].reserve(sizeof(RowRec) * (size_t)n_total * tiles_y + 16)) return -1;
+        if (ctx->work[ROW_CNT].reserve(sizeof(int) * (size_t)B * tiles_y)) return -1;
     }
-    ctx->r_plan.valid = true; ctx->r_plan.rowbin = rowbin;
-    ctx->r_plan.B = B; ctx->r_plan.W = W; ctx->r_plan.H = H; ctx->r_plan.n_total = n_total;
+    plan.valid = true; plan.rowbin = rowbin;
+    plan.B = B; plan.W = W; plan.H = H; plan.n_total = n_total;
     return 0;
 }
 
 extern "C" int octa_rasterize_2d_draw(octa_ctx *ctx, uint8_t *d_out, void *stream_) {
     if (!ctx) { octa::set_error("octa_rasterize_2d: null ctx"); return -2; }
-    if (!ctx->r_plan.valid) { octa::set_error("octa_rasterize_2d_draw: no plan (octa_rasterize_2d_plan must precede every draw)"); return -2; }
+    octa::RasterPlan &plan = ctx->plan;
+    if (!plan.valid) { octa::set_error("octa_rasterize_2d_draw: no plan (octa_rasterize_2d_plan must precede every draw)"); return -2; }
     if (!d_out) { octa::set_error("octa_rasterize_2d: null pointer"); return -2; }
-    const int B = ctx->r_plan.B, W = ctx->r_plan.W, H = ctx->r_plan.H;
-    const long n_total = ctx->r_plan.n_total;
-    const bool rowbin = ctx->r_plan.rowbin;
-    ctx->r_plan.valid = false;                  // the scratch holds ONE plan; it is consumed here
+    const int B = plan.B, W = plan.W, H = plan.H;
+    const long n_total = plan.n_total;
+    plan.valid = false;                         // the context holds ONE plan; it is consumed here
     hipStream_t stream = (hipStream_t)stream_;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
+    const EdgeMeta *meta = plan.meta.as<EdgeMeta>();
+    const BBox16 *bbox = plan.bbox.as<BBox16>();
+    const long *edge_off = plan.edge_off.as<long>();
+    const int *side_off = plan.side_off.as<int>(), *block_sums = plan.block_sums.as<int>();
+    int *err_flag = &plan.counters.as<octa::RasterCounters>()->error;
+    int4 *sides = ctx->work[SIDES].as<int4>();
     if (n_total > 0)
-        hipLaunchKernelGGL(raster_tess_kernel, dim3((unsigned)((n_total + TESS_WG - 1) / TESS_WG)), dim3(TESS_WG), 0, stream, ctx->r_edge_meta.as<EdgeMeta>(), ctx->r_tile_count.as<int>(),
-                           ctx->r_seg_total.as<int>(), n_total, W, H, ctx->r_sides.as<int4>(), ctx->r_counters.as<int>());
+        hipLaunchKernelGGL(raster_tess_kernel, dim3((unsigned)((n_total + TESS_WG - 1) / TESS_WG)), dim3(TESS_WG), 0, stream, meta, side_off, block_sums,
+                           n_total, W, H, sides, err_flag);
     const int tiles_x = (W + ST - 1) / ST, tiles_y = (H + ST_Y - 1) / ST_Y;
-    const RowRec *row_list = nullptr;
-    const int *row_cnt = nullptr;
-    {
-        if (rowbin) {
-            hipLaunchKernelGGL(raster_rowbin_kernel, dim3((unsigned)tiles_y, (unsigned)B), dim3(256), 0, stream, ctx->r_ucount.as<BBox16>(),
-                               ctx->r_edge_off.as<long>(), H, tiles_y, ctx->r_tile_list.as<RowRec>(), ctx->r_tile_fill.as<int>(), ctx->r_edge_meta.as<EdgeMeta>(),
-                               ctx->r_tile_count.as<int>(), ctx->r_seg_total.as<int>());
-            row_list = ctx->r_tile_list.as<RowRec>();
-            row_cnt = ctx->r_tile_fill.as<int>();
-        }
-    }
+    RowRec *row_list = plan.rowbin ? ctx->work[ROW_LIST].as<RowRec>() : nullptr;
+    int *row_cnt = plan.rowbin ? ctx->work[ROW_CNT].as<int>() : nullptr;
+    if (plan.rowbin)
+        hipLaunchKernelGGL(raster_rowbin_kernel, dim3((unsigned)tiles_y, (unsigned)B), dim3(256), 0, stream, bbox, edge_off, H, tiles_y, row_list, row_cnt,
+                           meta, side_off, block_sums);
     dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)B);
-    hipLaunchKernelGGL((row_list ? raster_render_kernel<true> : raster_render_kernel<false>), grid, dim3(WG), 0, stream, ctx->r_edge_meta.as<EdgeMeta>(),
-                       ctx->r_ucount.as<BBox16>(), ctx->r_edge_off.as<long>(), ctx->r_sides.as<int4>(), ctx->r_tile_count.as<int>(),
-                       ctx->r_seg_total.as<int>(), W, H, tiles_x, tiles_y, d_out, ctx->r_counters.as<int>(), row_list, row_cnt);
+    hipLaunchKernelGGL((row_list ? raster_render_kernel<true> : raster_render_kernel<false>), grid, dim3(WG), 0, stream, meta, bbox, edge_off, sides,
+                       side_off, block_sums, W, H, tiles_x, tiles_y, d_out, err_flag, row_list, row_cnt);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1190,12 +1187,10 @@ extern "C" int octa_fs_dither(octa_ctx *ctx, int B, const uint8_t *d_in, int W, 
         if (pipe_on && W % 16 == 0 && (reinterpret_cast<size_t>(d_in) & 15) == 0 && (reinterpret_cast<size_t>(d_out) & 15) == 0 && n_bands >= 2 &&
             lds_pipe <= 150 * 1024) {
             const int nw = n_bands < 16 ? n_bands : 16;
-            // OCTA_DITHER_BURST = 16 | 32 | 64 pixels per store burst (development aid). Measured per 128 labels at 1216^2 (profiles/r05_raster_pmc.log):
-            // 16: 488 MB written, 1.94 ms; 32: 306 MB, 1.98 ms; 64: 227 MB, 2.14 ms (the shift queue); 4 (round 4): 613 MB. Default 32.
-            constexpr int burst = 32;      // pixels per store burst (16 / 32 / 64 measured in round 5: 32 ships)
-            auto kern = burst == 64 ? fs_dither_pipe_kernel<16> : (burst == 32 ? fs_dither_pipe_kernel<8> : fs_dither_pipe_kernel<4>);
-            OCTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pipe));
-            hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64 * nw), lds_pipe, stream, d_in, W, H, n_bands, d_out);
+            // 32 pixels (8 words) per store burst. Measured per 128 labels at 1216^2 (profiles/r05_raster_pmc.log), pixels per burst:
+            // 16: 488 MB written, 1.94 ms; 32: 306 MB, 1.98 ms; 64: 227 MB, 2.14 ms (the shift queue); 4 (round 4): 613 MB. 32 ships.
+            OCTA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(fs_dither_pipe_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pipe));
+            hipLaunchKernelGGL(fs_dither_pipe_kernel<8>, dim3((unsigned)B), dim3(64 * nw), lds_pipe, stream, d_in, W, H, n_bands, d_out);
             OCTA_HIP_CHECK(hipGetLastError());
             return 0;
         }
@@ -1236,8 +1231,8 @@ extern "C" int octa_max_u8(octa_ctx *ctx, const uint8_t *d_a, const uint8_t *d_b
 extern "C" int octa_raster_prof(octa_ctx *ctx, int64_t *h_out4) {
     if (!ctx || !h_out4) return -2;
     OCTA_HIP_CHECK(hipSetDevice(ctx->device));
-    long tmp[8] = {0};
-    if (ctx->r_counters.p) OCTA_HIP_CHECK(hipMemcpy(tmp, ctx->r_counters.p, sizeof(tmp), hipMemcpyDeviceToHost));
-    h_out4[0] = tmp[0] & 0xffffffff; h_out4[1] = tmp[1]; h_out4[2] = tmp[2]; h_out4[3] = tmp[3];
+    octa::RasterCounters c = {};
+    if (ctx->plan.counters.p) OCTA_HIP_CHECK(hipMemcpy(&c, ctx->plan.counters.p, sizeof(c), hipMemcpyDeviceToHost));
+    h_out4[0] = (unsigned)c.error; h_out4[1] = c.prof[0]; h_out4[2] = c.prof[1]; h_out4[3] = c.prof[2];
     return 0;
 }

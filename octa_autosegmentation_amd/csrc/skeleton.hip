@@ -131,11 +131,11 @@ extern "C" int octa_skeletonize(octa_ctx *ctx, const uint8_t *d_in, int B, int H
     // no proof covers every shape. Running into it is a loud -3 on a call that was still converging, never a wrong skeleton.
     const int bound = H + W + SKEL_CHUNK;
     const int max_chunks = (bound + SKEL_CHUNK - 1) / SKEL_CHUNK;
-    if (ctx->r_tile_fill.reserve(sizeof(u64) * 2 * (size_t)n_words)) return -1;
-    if (ctx->r_tile_list.reserve(sizeof(int) * (size_t)SKEL_CHUNK * B * 2)) return -1;
-    u64 *A = ctx->r_tile_fill.as<u64>(), *Bp = A + n_words;
+    u64 *A = ctx->work[2].take<u64>(2 * (size_t)n_words);
     // flags of two chunks, alternating: a chunk's first double pass reads the last flags of the chunk before it
-    int *flags = ctx->r_tile_list.as<int>();
+    int *flags = ctx->work[1].take<int>((size_t)SKEL_CHUNK * B * 2);
+    if (!A || !flags) return -1;
+    u64 *Bp = A + n_words;
     std::vector<int> h_flags((size_t)SKEL_CHUNK * B);
 
     hipLaunchKernelGGL(skel_pack_kernel, dim3((unsigned)((n_words + 3) / 4)), dim3(256), 0, stream, d_in, A, H, W, Wq, n_words);

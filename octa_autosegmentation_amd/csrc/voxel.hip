@@ -138,9 +138,10 @@ extern "C" int octa_voxelize_3d(octa_ctx *ctx, int B, const double *d_edges, con
     if (h_edge_off[0] != 0) { octa::set_error("octa_voxelize_3d: offsets must start at 0"); return -2; }
     const size_t vox = (size_t)P.pd[0] * P.pd[1] * P.pd[2];
     const size_t vol_bytes = ((vox * (size_t)B + 15) / 16) * 16;
-    if (ctx->r_sides.reserve(vol_bytes + 16)) return -1;
-    if (ctx->r_seg_total.reserve(sizeof(long) * (size_t)(n_total + 1))) return -1;
-    OCTA_HIP_CHECK(hipMemsetAsync(ctx->r_sides.p, 0, vol_bytes, stream));
+    unsigned char *vol = ctx->work[0].take<unsigned char>(vol_bytes + 16);
+    long *d_img = ctx->work[3].take<long>((size_t)(n_total + 1));      // per edge: the image (graph) it belongs to
+    if (!vol || !d_img) return -1;
+    OCTA_HIP_CHECK(hipMemsetAsync(vol, 0, vol_bytes, stream));
     if (n_total > 0) {
         if (!d_edges) { octa::set_error("octa_voxelize_3d: null edges"); return -2; }
         std::vector<long> img((size_t)n_total);
@@ -148,16 +149,14 @@ extern "C" int octa_voxelize_3d(octa_ctx *ctx, int B, const double *d_edges, con
             if (h_edge_off[b + 1] < h_edge_off[b]) { octa::set_error("octa_voxelize_3d: offsets must be non-decreasing"); return -2; }
             for (long i = h_edge_off[b]; i < h_edge_off[b + 1]; i++) img[(size_t)i] = b;
         }
-        OCTA_HIP_CHECK(hipMemcpyAsync(ctx->r_seg_total.p, img.data(), sizeof(long) * n_total, hipMemcpyHostToDevice, stream));
+        OCTA_HIP_CHECK(hipMemcpyAsync(d_img, img.data(), sizeof(long) * n_total, hipMemcpyHostToDevice, stream));
         OCTA_HIP_CHECK(hipStreamSynchronize(stream));  // img goes out of scope
-        hipLaunchKernelGGL(voxel_edges_kernel, dim3((unsigned)n_total), dim3(256), 0, stream, d_edges, d_keep,
-                           ctx->r_seg_total.as<long>(), n_total, P, ctx->r_sides.as<unsigned char>());
+        hipLaunchKernelGGL(voxel_edges_kernel, dim3((unsigned)n_total), dim3(256), 0, stream, d_edges, d_keep, d_img, n_total, P, vol);
         OCTA_HIP_CHECK(hipGetLastError());
     }
     const size_t n = vox * (size_t)B;
     const size_t threads = (n + 15) / 16;
-    hipLaunchKernelGGL(voxel_widen_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream,
-                       ctx->r_sides.as<unsigned char>(), d_out, n);
+    hipLaunchKernelGGL(voxel_widen_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, vol, d_out, n);
     OCTA_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -59,8 +59,9 @@ def select_edges(forest, min_radius=0, max_radius=1, max_dropout_prob=0, blackdi
 
 def rasterize_edges_device_plan(d_edges, edge_off, image_resolution, MIP_axis=2, min_radius=0.0, max_radius=1.0, d_keep=None):
     """First half of rasterize_edges_device (octa_rasterize_2d_plan): the per-edge records and the side-offset scan, with the
-    rasteriser's one host synchronisation. Returns the token rasterize_edges_device_draw takes; the context's scratch holds ONE plan,
-    so plan and draw of a call pair must not be interleaved with another pair on the same context (_native.use_ctx)."""
+    rasteriser's one host synchronisation. Returns the token rasterize_edges_device_draw takes. A context holds ONE plan: a second plan
+    (or a rasterize_edges_device) on the same context (_native.use_ctx) replaces the first; any other entry point may run on that context
+    between plan and draw, on the same stream."""
     import torch
     no_pixels_x, no_pixels_y = int(image_resolution[0]), int(image_resolution[1])
     edge_off = np.ascontiguousarray(edge_off, dtype=np.int64)

@@ -67,6 +67,96 @@ def test_plan_and_draw_are_the_two_halves_of_one_call(t2i, raster_golden):
         _native.free_ctx(b)
 
 
+def _other_calls(t2i):
+    """name -> a call of another module on the calling thread's context (small seeded inputs), returning its result tensors. Between
+    them they take every work buffer the draw half uses, and the voxeliser's per-edge index besides."""
+    import torch
+    from octa_autosegmentation_amd import _native, graph_io
+    from octa_autosegmentation_amd.models import postprocess
+    from octa_autosegmentation_amd.utils import skeleton
+    rng = np.random.default_rng(7)
+    vox_edges = torch.from_numpy(np.array([[0.2, 0.2, 0.2, 0.7, 0.6, 0.5, 0.06], [0.1, 0.8, 0.3, 0.6, 0.2, 0.7, 0.05],
+                                           [0.5, 0.5, 0.1, 0.5, 0.5, 0.9, 0.08]])).cuda()
+    vol = torch.from_numpy((rng.random((1, 4, 8, 8)) > 0.5).astype(np.uint8)).cuda()
+    img = torch.from_numpy((rng.random((1, 8, 8)) > 0.4).astype(np.uint8)).cuda()
+    x = torch.from_numpy(rng.standard_normal((1, 2, 64)).astype(np.float32)).cuda()
+    rows = torch.from_numpy(rng.random((3, 7))).cuda()
+
+    def instnorm():
+        y, mean, rstd = torch.empty_like(x), torch.empty(2, device="cuda"), torch.empty(2, device="cuda")
+        _native.launch("octa_instnorm_lrelu_fwd", x.device, x, y, None, None, mean, rstd, 1, 2, 64, 0, 0.01, 1e-5)
+        return y, mean, rstd
+
+    return {
+        "voxelize_edges_device": lambda: (t2i.voxelize_edges_device(vox_edges, np.array([0, 1, 3]), [8, 8, 8]),),
+        "octa_cc3d_filter": lambda: postprocess.cc3d_filter_device(vol, 3, 0, min_size=3, return_info=True),
+        "octa_remove_small_objects": lambda: (postprocess.remove_small_objects_device(img, min_size=3),),
+        "octa_skeletonize": lambda: (skeleton.skeletonize_device(img),),
+        "octa_instnorm_lrelu_fwd": instnorm,
+        "edges_as_read_back_device": lambda: (graph_io.edges_as_read_back_device(rows),),
+    }
+
+
+OTHER_CALLS = ["voxelize_edges_device", "octa_cc3d_filter", "octa_remove_small_objects", "octa_skeletonize", "octa_instnorm_lrelu_fwd",
+               "edges_as_read_back_device"]
+
+
+@pytest.mark.parametrize("other", OTHER_CALLS)
+def test_other_calls_between_plan_and_draw_leave_the_plan_intact(t2i, raster_golden, other):
+    """A context holds one plan, and any other entry point may run on it between plan and draw (include/octa_hip.h): graph 0 has
+    13 821 edges, so four scan blocks whose bases are not all zero, and the draw after the other call gives the golden image bit for
+    bit; the other call gives what it gives on a fresh context."""
+    import torch
+    from octa_autosegmentation_amd import _native
+    e0 = np.asarray(raster_golden["graph0_edges"], np.float64)
+    assert len(e0) > 3 * 4096
+    d = torch.from_numpy(e0).cuda()
+    call = _other_calls(t2i)[other]
+    fresh, held = _native.new_ctx(), _native.new_ctx()
+    try:
+        with _native.use_ctx(fresh):
+            want = [t.cpu() for t in call()]
+        with _native.use_ctx(held):
+            plan = t2i.rasterize_edges_device_plan(d, np.array([0, len(e0)]), [304, 304])
+            got = [t.cpu() for t in call()]
+            out = t2i.rasterize_edges_device_draw(plan).cpu().numpy()
+        assert (out[0] == raster_golden["graph0_img304"]).all()
+        assert len(got) == len(want) and all(torch.equal(a, b) for a, b in zip(got, want))
+    finally:
+        _native.free_ctx(fresh)
+        _native.free_ctx(held)
+
+
+def test_scratch_bytes_counts_every_buffer_and_reaches_a_steady_state(t2i, raster_golden):
+    """octa_ctx_scratch_bytes counts everything the context holds (0 when fresh, the norm kernels' ring of pre-zeroed slots -- 4 MiB at
+    least -- after one channels-last norm without statistics from outside), and no buffer grows on a second call of the same shapes."""
+    import torch
+    from octa_autosegmentation_amd import _native
+    held = lambda: _native.lib().octa_ctx_scratch_bytes(h)
+    e0 = np.asarray(raster_golden["graph0_edges"], np.float64)
+    d = torch.from_numpy(e0).cuda()
+    calls = _other_calls(t2i)
+    h = _native.new_ctx()
+    try:
+        assert held() == 0
+        with _native.use_ctx(h):
+            x = torch.from_numpy(np.random.default_rng(3).standard_normal((1, 8, 8, 32)).astype(np.float32)).cuda().to(torch.bfloat16)
+            y, mean, rstd = torch.empty_like(x), torch.empty(32, device="cuda"), torch.empty(32, device="cuda")
+            _native.launch("octa_instnorm_lrelu_nhwc_fwd", x.device, x, y, None, None, mean, rstd, 1, 32, 64, 0.01, 1e-5, None, 0, None, 0)
+            assert held() >= 4 << 20
+            rounds = []
+            for _ in range(3):
+                plan = t2i.rasterize_edges_device_plan(d, np.array([0, len(e0)]), [304, 304])
+                for name in OTHER_CALLS:
+                    calls[name]()
+                t2i.rasterize_edges_device_draw(plan)
+                rounds.append(held())
+            torch.cuda.synchronize()
+        assert rounds[0] == rounds[1] == rounds[2]
+    finally:
+        _native.free_ctx(h)
+
+
 def test_labels_bit_exact(t2i, raster_golden):
     import torch
     g = raster_golden
