@@ -523,6 +523,37 @@ int octa_dice_bce_finish(octa_ctx *ctx, const double *d_sums, int B, int64_t n, 
 int octa_dice_bce_bwd(octa_ctx *ctx, const void *d_logits, int dtype, const float *d_y, int B, int64_t n, const double *d_sums,
                       const float *d_grad_out, float smooth_nr, float smooth_dr, void *d_dlogits, void *stream);
 
+/* ---- the elementwise tail of the CycleGAN step (csrc/gan_loss.hip) ---------
+ * models/cycle_gan.py:169-228: cycle and identity L1 terms, LSGAN terms, background mixing, image pool. dtype 0 = float32,
+ * 1 = bfloat16. h_* arrays live on the HOST (they hold device pointers, counts and weights and travel as kernel arguments);
+ * d_* pointers are device memory. Every sum is taken in double in a fixed order: two runs give the same bits.
+ *
+ * K <= 4 weighted L1 terms: d_sums double[K] = sum |pred_k - target_k| over n_k elements; finish writes float32 d_out[K + 1] =
+ * (w_k sums_k / n_k ..., their total); bwd writes d pred_k = g * float(w_k / n_k) * sign(pred_k - target_k) (sign(0) = 0) in pred's
+ * dtype, g = d_grad_out[0], the gradient of the total. All pred share pred_dtype, all targets target_dtype. */
+int octa_l1_pairs_fwd(octa_ctx *ctx, int K, const void *const *h_pred, const void *const *h_target, const int64_t *h_n, int pred_dtype,
+                      int target_dtype, double *d_sums, void *stream);
+int octa_l1_pairs_finish(octa_ctx *ctx, int K, const double *d_sums, const int64_t *h_n, const double *h_w, float *d_out, void *stream);
+int octa_l1_pairs_bwd(octa_ctx *ctx, int K, const void *const *h_pred, const void *const *h_target, const int64_t *h_n, const double *h_w,
+                      int pred_dtype, int target_dtype, const float *d_grad_out, void *const *h_dpred, void *stream);
+/* T <= 2 LSGAN terms (utils/losses.py:183-202 on a PatchGAN map): d_sums double[T] = sum (p_k - target_k)^2, d_loss float32[T + 1] =
+ * (scale_k sums_k / n_k ..., their total); bwd writes d p_k = g * float(2 scale_k / n_k) * (p_k - target_k) in p's dtype. */
+int octa_lsgan_fwd(octa_ctx *ctx, int T, const void *const *h_p, const int64_t *h_n, const float *h_target, const double *h_scale, int dtype,
+                   double *d_sums, float *d_loss, void *stream);
+int octa_lsgan_bwd(octa_ctx *ctx, int T, const void *const *h_p, const int64_t *h_n, const float *h_target, const double *h_scale, int dtype,
+                   const float *d_grad_out, void *const *h_dp, void *stream);
+/* out = max(x, m), m = bg * u rounded to bg's dtype (models/cycle_gan.py:171-176: torch.maximum(real_A, background * uniform)); out and
+ * dout are bfloat16 when x_dtype and m_dtype both are, float32 otherwise. bwd: dx = dout where x > m, dout / 2 where x == m, 0 where
+ * x < m, in x's dtype. */
+int octa_mix_max_fwd(octa_ctx *ctx, const void *d_x, int x_dtype, const void *d_bg, const void *d_u, int m_dtype, int64_t n, void *d_out, void *stream);
+int octa_mix_max_bwd(octa_ctx *ctx, const void *d_x, int x_dtype, const void *d_bg, const void *d_u, int m_dtype, int64_t n, const void *d_dout,
+                     void *d_dx, void *stream);
+/* One query of the image pool (models/cycle_gan.py:287-336) resolved by the host into two tables. d_pool [pool_size][elems], d_in and
+ * d_out [B][elems] (B <= 32), no two of them overlapping. h_src[b]: k >= 0 = returned image b is input k, -1 - s = it is the content
+ * slot s had BEFORE this call. h_wslot[j] / h_winput[j], j < nw: slot wslot[j] ends up holding input winput[j]; every slot at most once. */
+int octa_pool_exchange(octa_ctx *ctx, void *d_pool, int pool_size, const void *d_in, int B, void *d_out, int64_t elems, int dtype, const int *h_src,
+                       int nw, const int *h_wslot, const int *h_winput, void *stream);
+
 /* ---- convolutions with ONE channel on one side: the GAN networks' stems and heads ----
  * Replace nn.Conv2d(1, 64, 7) / nn.Conv2d(64, 1, 7) of ResnetGenerator (models/networks.py:360-368, behind ReflectionPad2d(3)) and
  * nn.Conv2d(1, 64, 4, 1, 1) / nn.Conv2d(512, 1, 4, 1, 1) of NLayerDiscriminator (:433-442) -- forward, data gradient and weight

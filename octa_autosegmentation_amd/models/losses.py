@@ -91,7 +91,7 @@ def _at_loss(config, scaler=None, loss=None, **kwargs):
 
 def get_loss_function_by_name(name: str, config=None, *args, **kwargs):
     table = {"DiceBCELoss": lambda: DiceBCELoss(True), "LSGANLoss": LSGANLoss,
-             "BCELoss": lambda: torch.nn.BCEWithLogitsLoss(), "MSELoss": torch.nn.MSELoss,
+             "BCELoss": lambda: torch.nn.BCEWithLogitsLoss(), "MSELoss": torch.nn.MSELoss, "L1Loss": torch.nn.L1Loss,
              "AtLoss": lambda: _at_loss(config, *args, **kwargs)}
     if name not in table:
         raise NotImplementedError(f"loss {name} is outside the MI355X hot path")

@@ -647,10 +647,12 @@ from .gan_seg_model import GanSegModel  # noqa: E402  (it receives MODEL_DICT th
 from .oof import OOF  # noqa: E402
 from .frangi import Frangi  # noqa: E402
 from .skrgan import SkrGAN  # noqa: E402
+from .cycle_gan import CycleGAN  # noqa: E402
 
 # reference models/networks.py:1009-1026 restricted to the hot path: the segmentation network, the contrast-adaptation
-# generator / discriminator and the joint model; the paper's other GAN baselines are out of scope
+# generator / discriminator and the joint model; of the paper's unpaired-translation baselines CycleGAN (models/cycle_gan.py,
+# csrc/gan_loss.hip), the other four (CUT, NEGCUT, DCLGAN, NICE-GAN) are out of scope
 # + the classical OOF, Frangi and sketch-filter baselines (reference models/oof.py, models/frangi.py, models/skrgan.py,
 # configs/config_oof.yml, configs/config_frangi.yml; csrc/oof.hip, csrc/frangi.hip, csrc/morph.hip)
 MODEL_DICT = {"DynUNet": DynUNet, "resnetGenerator9": resnetGenerator9, "patchGAN70x70": patchGAN70x70, "GanSegModel": GanSegModel, "oof": OOF,
-              "frangi": Frangi, "skrgan": SkrGAN}
+              "frangi": Frangi, "skrgan": SkrGAN, "CycleGAN": CycleGAN}
