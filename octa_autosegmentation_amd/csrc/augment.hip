@@ -11,8 +11,10 @@
 //                            (F.affine_grid + F.grid_sample, bilinear, zeros padding, align_corners = False arithmetic),
 //                            the exact index permutations of the preceding flip / rot90 folded into the tap addresses,
 //                            optional threshold (AsDiscrete) on the way out.
-// MONAI itself is not in the image (parity with it is unpinned); the kernels are pinned against the torch
-// ops MONAI delegates to (tests/test_augment_gpu.py).
+// MONAI itself is not in the image (parity with it is unpinned); the kernels are pinned to float64 definitions
+// of the torch ops MONAI delegates to, with derived bounds: the resize pair in tests/_resize_ref.py (tests/test_resize_gpu.py),
+// rotate_kernel and its window form in tests/_rotate_ref.py (tests/test_rotate_gpu.py), the speckle passes and the background
+// blend in tests/_speckle_ref.py (tests/test_speckle_gpu.py), the whole chain in tests/test_augment_gpu.py.
 
 #include "common.h"
 

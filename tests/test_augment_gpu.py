@@ -1,10 +1,24 @@
 """GPU parity of the augmentation kernels (csrc/augment.hip) against the torch ops MONAI's transforms delegate to:
 F.interpolate(bilinear), torch.flip / torch.rot90, F.affine_grid + F.grid_sample. fp32, tolerance 1e-5 (same formulas,
-fused multiply-adds may differ in the last bits)."""
+fused multiply-adds may differ in the last bits).
+The derived bounds now live in tests/_rotate_ref.py and tests/_speckle_ref.py (held by tests/test_rotate_gpu.py and tests/test_speckle_gpu.py);
+this file keeps the torch-parity smoke checks and holds the whole chain to the composition of the float64 references."""
+import random
+
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
+
+CHAIN_CONFIG = [{"name": "LoadGraphAndFilterByRandomRadiusd", "keys": ["image", "label"]},
+                {"name": "ScaleIntensityd", "keys": ["image", "label"], "minv": 0, "maxv": 1},
+                {"name": "EnsureChannelFirstd", "keys": ["image", "label"]},
+                {"name": "Resized", "keys": ["image", "label"], "spatial_size": [128, 128], "mode": "bilinear"},
+                {"name": "RandFlipd", "keys": ["image", "label"], "prob": 0.5, "spatial_axis": [0, 1]},
+                {"name": "RandRotate90d", "keys": ["image", "label"], "prob": 0.75},
+                {"name": "RandRotated", "keys": ["image", "label"], "prob": 1, "range_x": 0.1745, "padding_mode": "zeros"},
+                {"name": "AsDiscreted", "keys": ["label"], "threshold": 0.1},
+                {"name": "CastToTyped", "keys": ["image", "label"], "dtype": "dtype"}]
 
 
 def test_resize_matches_torch_interpolate(hip_lib_built):
@@ -81,15 +95,7 @@ def test_augmentation_chain_from_config(hip_lib_built):
     """The reference's config list drives the chain; image and label of a sample get the same geometry."""
     import torch
     from octa_autosegmentation_amd.data import gpu_augment
-    cfg = [{"name": "LoadGraphAndFilterByRandomRadiusd", "keys": ["image", "label"]},
-           {"name": "ScaleIntensityd", "keys": ["image", "label"], "minv": 0, "maxv": 1},
-           {"name": "EnsureChannelFirstd", "keys": ["image", "label"]},
-           {"name": "Resized", "keys": ["image", "label"], "spatial_size": [128, 128], "mode": "bilinear"},
-           {"name": "RandFlipd", "keys": ["image", "label"], "prob": 0.5, "spatial_axis": [0, 1]},
-           {"name": "RandRotate90d", "keys": ["image", "label"], "prob": 0.75},
-           {"name": "RandRotated", "keys": ["image", "label"], "prob": 1, "range_x": 0.1745, "padding_mode": "zeros"},
-           {"name": "AsDiscreted", "keys": ["label"], "threshold": 0.1},
-           {"name": "CastToTyped", "keys": ["image", "label"], "dtype": "dtype"}]
+    cfg = CHAIN_CONFIG
     aug = gpu_augment.GpuSegAugmentation(cfg, seed=3)
     g = torch.Generator(device="cuda").manual_seed(4)
     img = torch.randint(0, 256, (6, 32, 32), device="cuda", generator=g, dtype=torch.uint8)
@@ -103,6 +109,82 @@ def test_augmentation_chain_from_config(hip_lib_built):
     # same seed -> same decisions
     again = gpu_augment.GpuSegAugmentation(cfg, seed=3)(img, lab)
     assert torch.equal(again["image"], out["image"]) and torch.equal(again["label"], out["label"])
+
+
+def _composition(x, size, params, win=None):
+    """What the chain is configured to compute, in float64 on the inputs' device: ScaleIntensity(0, 1) with each image's own minimum and
+    maximum (a constant image maps to minv), the bilinear resize of tests/_resize_ref.py, then the flip / rot90 / rotation of
+    tests/_rotate_ref.py with the decisions the object reports. -> (reference before the threshold, tolerance): the rotate bound, with
+    the resize bound carried through the rotation (the four weights sum to at most 1) and three roundings for the scale map, which the
+    object forms in fp32 (1 / span, min * mul, minv - that)."""
+    import torch
+    import _resize_ref as rr
+    import _rotate_ref as R
+    xd = x.double()
+    mn, mx = xd.amin((1, 2)), xd.amax((1, 2))
+    span = mx - mn
+    mul = torch.where(span > 0, 1.0 / span, torch.zeros_like(span))
+    add = 0.0 - mn * mul
+    y, tol_y = rr.forward(x, size[0], size[1], mul, add)
+    scale = rr.U * (xd.abs().amax((1, 2)) * mul + 2.0 * mn.abs() * mul + add.abs())
+    angle = torch.from_numpy(params["angle"]).to(x.device)
+    return R.reference(y, angle, params["rot_k"], params["flip"], win=win, extra=tol_y.amax((1, 2)) + scale)
+
+
+def _chain_inputs():
+    """the batch of test_augmentation_chain_from_config with one constant image and one empty label in it (ScaleIntensity: mul = 0)"""
+    import torch
+    g = torch.Generator(device="cuda").manual_seed(4)
+    img = torch.randint(0, 256, (6, 32, 32), device="cuda", generator=g, dtype=torch.uint8)
+    lab = (torch.rand(6, 128, 128, device="cuda", generator=g) > 0.7).to(torch.uint8) * 255
+    img[2], lab[2] = 77, 0
+    return img, lab
+
+
+def _check_chain(out, img, lab, win=None):
+    import torch
+    import _rotate_ref as R
+    p = out["params"]
+    assert len(set(p["rot_k"].tolist())) > 1 and len(set(p["flip"].tolist())) == 2 and np.abs(p["angle"]).min() > 0
+    ref, tol = _composition(img, (128, 128), p, win)
+    rat = R.ratio(out["image"][:, 0], ref, tol)
+    lref, ltol = _composition(lab, (128, 128), p, win)
+    share = float((~R.decided(lref, ltol, 0.1)).sum((1, 2)).max()) / (lref.shape[1] * lref.shape[2])
+    wrong, other = R.discrete(out["label"][:, 0], lref, ltol, 0.1)
+    print("CHAIN", tuple(out["image"].shape), "image error / bound", float(f"{rat:.4g}"), "label: undecided share", share, "wrong", wrong, "not 0 or 1", other)
+    assert rat <= 1.0
+    assert share <= R.UNDECIDED_CAP and wrong == 0 and other == 0
+    # the constant image is minv everywhere in front of the rotation, the empty label 0 behind the threshold: exactly
+    assert bool((out["image"][2] == 0).all()) and bool((out["label"][2] == 0).all())
+    assert float(out["label"].mean()) > 0.1 and float(out["image"].mean()) > 0.2
+
+
+def test_augmentation_chain_is_the_configured_composition(hip_lib_built):
+    """out["image"] and out["label"] ARE ScaleIntensity, Resized, flip, rot90 and rotation with the reported decisions, within the derived
+    bounds; the label exactly on every decided pixel. Measured on an MI355X on the kernels of commit c9efa0d: image error / bound 0.060
+    (0.041 in the 64 x 64 windows), 0.15 % of a label at most undecided, no decided pixel wrong."""
+    from octa_autosegmentation_amd.data import gpu_augment
+    img, lab = _chain_inputs()
+    out = gpu_augment.GpuSegAugmentation(CHAIN_CONFIG, seed=3)(img, lab)
+    assert out["image"].shape == out["label"].shape == (6, 1, 128, 128)
+    _check_chain(out, img, lab)
+
+
+@pytest.mark.parametrize("factor", [0.5, 1.25])
+def test_augmentation_chain_with_the_crop_is_the_window_of_the_composition(hip_lib_built, factor):
+    """with a RandCropOrPadd entry behind RandRotated: the reported window of that same composition (factor 1.25: the pad, negative offsets)"""
+    from octa_autosegmentation_amd.data import gpu_augment
+    cfg = CHAIN_CONFIG[:7] + [{"name": "RandCropOrPadd", "keys": ["image", "label"], "prob": 1, "min_factor": factor, "max_factor": factor}] + CHAIN_CONFIG[7:]
+    img, lab = _chain_inputs()
+    random.seed(7)
+    out = gpu_augment.GpuSegAugmentation(cfg, seed=3)(img, lab)
+    side = int(128 * factor)
+    assert out["image"].shape == out["label"].shape == (6, 1, side, side)
+    offs = list(zip(out["params"]["crop_oy"].tolist(), out["params"]["crop_ox"].tolist()))
+    assert (len(set(offs)) > 1 and min(min(o) for o in offs) >= 0) if factor < 1 else offs == [(-16, -16)] * 6
+    _check_chain(out, img, lab, ((side, side), offs))
+    plain = gpu_augment.GpuSegAugmentation(CHAIN_CONFIG, seed=3)(img, lab)            # same seed, same decisions: the window of the full frame
+    assert np.array_equal(plain["params"]["angle"], out["params"]["angle"]) and np.array_equal(plain["params"]["rot_k"], out["params"]["rot_k"])
 
 
 def test_noise_kernels_match_the_reference_fixture(hip_lib_built):
